@@ -6,9 +6,15 @@
 
 One process per GPU.  A "step" is one pass of the hot path over one batch of synthetic input that is already resident
 in HBM: every forward command, every backward command, (N > 1: RCCL all-reduce of every parameter gradient over xGMI),
-one SGD command per parameter tensor.  Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events around
-every launch of the contraction kernel (in-library, on the launching stream); `cpu_baseline` times the reference's own
-lib/nnc CPU backend (oracle/_ref) on one image of the same network on this host.
+one SGD command per parameter tensor.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...).  `--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy (float32; a
+fixed, seeded sample of each large tensor).  Everything else is measured or checked only with `--full`: the HIP-graph
+capture and other-ReLU legs, `roofline` (HIP events around every launch of the contraction kernel, in-library, on the
+launching stream), the drop-in number through the reference host (`via_host`), `cpu_baseline` (the reference's own
+lib/nnc CPU backend, oracle/_ref, on one image of the same network on this host) with its step-1 oracle gate, the
+data-parallel exchange check (N > 1) and the default run's `extra_configs`.
 """
 import argparse
 import json
@@ -246,7 +252,7 @@ def resnet_config(args, half, dawn=False):
         issued_ms = (cap.get("issued_per_command_ms_per_step") or 0.0) if cap.get("on") else 0.0
         out["config"]["host_enqueue"] = dict(he, devices_one_thread_can_feed=(issued_ms or h["ms_per_step"]) / he["ms_per_step_median"] if he["ms_per_step_median"] > 0 else None,
                                              note="wall time of the step call on drained streams, one host thread, one device; the step's GPU time / this = how many devices that thread keeps busy")
-    if not args.no_cpu_baseline and devices == 1:
+    if args.full and not args.no_cpu_baseline and devices == 1:
         out["cpu_baseline"], out["config"]["oracle_gate"] = host_cpu_baseline(args, half, dawn)
     emit(out)
 
@@ -357,6 +363,48 @@ def pmc_traffic(symbol, batch):
     return tot / n if n else None
 
 
+DUMP_SAMPLE = 1 << 18  # elements kept of a larger tensor by --dump-outputs (VGG-D: under 40 MB in all)
+DUMP_LIMIT = 64 << 20
+
+
+def vgg_outputs(net, fwd_only):
+    """(name, host array) of what a caller of the timed step receives: per-image loss and softmax; a training step also the updated parameters and their
+    gradients, named after the layer (conv01 .. conv13, fc14 .. fc16).  Gradients that are slices of one arena (N > 1) are read back from one copy of it."""
+    owners = {}
+
+    def host(t):
+        if t.owner is None:
+            return t.numpy()
+        if id(t.owner) not in owners:
+            owners[id(t.owner)] = t.owner.numpy().reshape(-1)
+        off = (t.ptr - t.owner.ptr) // t.np_dtype.itemsize
+        return owners[id(t.owner)][off:off + int(np.prod(t.dims))].reshape(t.dims)
+    out = [("loss", host(net.loss)), ("softmax", host(net.softmax))]
+    if not fwd_only:
+        layer = 0
+        for n in net.nodes:
+            if n["kind"] in ("conv", "fc"):
+                layer += 1
+                for key, name in (("w", "weight"), ("bias", "bias"), ("dw", "weight_grad"), ("dbias", "bias_grad")):
+                    out.append(("%s%02d_%s" % (n["kind"], layer, name), host(n[key])))
+    return out
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32.  An array over DUMP_SAMPLE elements is reduced to a fixed sample of its flat positions (drawn
+    with seed = the array's place in the list, so every run and every build keeps the same positions), in position order."""
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for k, (name, a) in enumerate(arrays):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.size > DUMP_SAMPLE:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(k).choice(a.size, DUMP_SAMPLE, replace=False))]
+        total += a.nbytes
+        if total > DUMP_LIMIT:
+            raise SystemExit("bench.py: --dump-outputs would write more than %d bytes" % DUMP_LIMIT)
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 EXTRA_CONFIGS = ["vggd-fwd-bs64", "resnet50-nchw-bs256", "resnet50-nchw-bs256-f16", "cifar10-dawn-f16-bs512", "imdb-lstm-bs64"]
 
 
@@ -371,7 +419,7 @@ def extra_configs(args):
     cache = tempfile.mkdtemp(prefix="nnc_bench_cpu_")
     for name in EXTRA_CONFIGS:
         t0 = time.time()
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", "5", "--warmup", "2", "--no-extra-configs", "--no-alt-leg"]
+        cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", "5", "--warmup", "2", "--full", "--no-extra-configs", "--no-alt-leg"]
         if args.no_cpu_baseline:
             cmd.append("--no-cpu-baseline")
         try:
@@ -527,8 +575,14 @@ def main():
     ap.add_argument("--no-extra-configs", action="store_true", help="the default run (config 3, one GPU) ends with a short run of configs 2, 4, 4-f16 and 5 whose lines it carries in `extra_configs`; this skips them")
     ap.add_argument("--no-capture", action="store_true", help="skip the HIP-graph capture legs (SURVEY.md 8(f)3): time only the steps issued command by command")
     ap.add_argument("--no-via-host", action="store_true", help="skip the second driver: the same step through the reference host's symbolic graph / autotune / static schedule (tools/host_vgg_bench.c)")
-    ap.add_argument("--records", default=None, help="also write the per-launch contraction records (name, dims, ms, TFLOP/s) of the roofline leg to this file")
+    ap.add_argument("--records", default=None, help="also write the per-launch contraction records (name, dims, ms, TFLOP/s) of the roofline leg to this file (--full)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: capture / other-ReLU / roofline legs, via-host driver, CPU baseline and oracle gate, "
+                    "data-parallel check, extra configs (the --no-* options switch single ones off); a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write what the last one computed as DIR/<name>.npy (float32; "
+                    "loss, softmax, updated parameters and their gradients, a fixed seeded sample of each large tensor)")
     args = ap.parse_args()
+    if args.dump_outputs and args.config not in ("vggd-train-bs256", "vggd-fwd-bs64"):
+        raise SystemExit("bench.py: --dump-outputs is available for the VGG-D configs (the other configs are timed inside the reference host's harness)")
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -637,11 +691,11 @@ def main():
             return {"ok": False, "error": str(e)}
 
     for i in range(args.warmup):
-        if i == 0 and comm and not fwd_only:
+        if i == 0 and comm and not fwd_only and args.full:
             dp_check = checked_first_step()
         else:
             step()
-        if i == 0:
+        if i == 0 and args.full:
             L.stream_wait(stream)
             step1_losses = net.loss.numpy()[:8].astype(np.float64)
             step1_loss = float(step1_losses[0])
@@ -658,11 +712,13 @@ def main():
     if dist:
         dt = dist.reduce_max(dt)
     loss = float(net.loss.numpy().mean())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, vgg_outputs(net, fwd_only))
 
     # HIP-graph capture of the step: the same step recorded once and replayed K times -- one runtime call per step instead of ~150 commands.
     # One GPU only here (the N-GPU form's gradient exchange goes through torch.distributed, outside this library's streams).  Reported beside the headline.
     dt_cap = cap_nodes = None
-    if world == 1 and not args.no_capture:
+    if world == 1 and args.full and not args.no_capture:
         if L.capture_begin(stream) == 0:
             step()
             graph = L.capture_end(stream)
@@ -681,7 +737,7 @@ def main():
     # The library's look-ahead (peephole.cpp) would fold the separately issued ReLUs as well -- it is what gives the reference host the
     # same saving (via_host) -- so it is switched off for this leg: what is timed is the step with every ReLU as its own pass.
     dt_alt = None
-    if not args.no_alt_leg:
+    if args.full and not args.no_alt_leg:
         net.fuse_relu = not net.fuse_relu
         L.dll.nnc_mi355x_set_peephole(0)
         step()
@@ -699,12 +755,14 @@ def main():
     # roofline leg: three more steps with every contraction launch bracketed by HIP events on its stream; per launch position
     # the MEDIAN of the three (one stalled launch -- an allocator call, a clock dip -- would otherwise skew a kernel's average)
     LEG = 3
-    L.profile_enable(1)
-    for _ in range(LEG):
-        step()
-    L.stream_wait(stream)
-    allrecs = L.profile_records()
-    L.profile_enable(0)
+    allrecs = []
+    if args.full:
+        L.profile_enable(1)
+        for _ in range(LEG):
+            step()
+        L.stream_wait(stream)
+        allrecs = L.profile_records()
+        L.profile_enable(0)
     per = len(allrecs) // LEG
     recs = []
     for i in range(per):
@@ -766,9 +824,9 @@ def main():
             # the drop-in number (the unmodified reference host driving this backend), next to `value` (ccv_amd/vgg.py, the command driver)
             out["via_host_images_per_s"] = out["config"]["via_host"].get("images_per_s")
             out["config"]["via_host_images_per_s"] = out["via_host_images_per_s"]  # (also inside `config`: the driver's parsed record keeps that object whole)
-        if not args.no_cpu_baseline and world > 1:
-            out["cpu_baseline"] = {"value": None, "unit": "images/s", "cores": 0, "kind": "reference", "sample": "timed at N = 1 only (python bench.py --gpus 1)"}
-        elif not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline and world > 1:
+            out["cpu_baseline"] = {"value": None, "unit": "images/s", "cores": 0, "kind": "reference", "sample": "timed at N = 1 only (python bench.py --gpus 1 --full)"}
+        elif args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"], oracle_loss = cpu_baseline(image0, label0, fwd_only)
             except Exception as e:  # the checker is optional for the bench line, never for the parity tests
@@ -781,7 +839,7 @@ def main():
                 if not rel <= 1e-4:
                     emit(out)
                     raise SystemExit("bench.py: step-1 loss of image 0 differs from the oracle's: %r vs %r (rel %.3g > 1e-4)" % (step1_loss, oracle_loss, rel))
-        if args.config == "vggd-train-bs256" and world == 1 and not args.no_extra_configs and not force_comm:
+        if args.full and args.config == "vggd-train-bs256" and world == 1 and not args.no_extra_configs and not force_comm:
             L.stream_wait(stream)
             out["extra_configs"] = extra_configs(args)
         emit(out)

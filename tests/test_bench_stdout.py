@@ -48,7 +48,7 @@ def test_self_launched_ranks_on_this_box():
     from ccv_amd import nnc
     n = nnc.load().device_count()
     env = dict(os.environ, NNC_BENCH_FORCE_SELF_LAUNCH="1", NNC_BENCH_FORCE_COMM="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--batch", "16", "--no-cpu-baseline", "--no-via-host", "--no-alt-leg"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--batch", "16", "--full", "--no-cpu-baseline", "--no-via-host", "--no-alt-leg"],
                        capture_output=True, text=True, timeout=1500, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = r.stdout.splitlines()
@@ -92,7 +92,7 @@ def test_launched_by_torch_distributed_run_as_the_driver_does():
     n = nnc.load().device_count()
     env = dict(os.environ, NNC_BENCH_FORCE_COMM="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1", "--master-port", "29533",
-                        os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--batch", "16", "--no-cpu-baseline", "--no-via-host", "--no-alt-leg", "--no-extra-configs"],
+                        os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--batch", "16", "--full", "--no-cpu-baseline", "--no-via-host", "--no-alt-leg", "--no-extra-configs"],
                        capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

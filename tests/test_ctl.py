@@ -2,11 +2,29 @@
 calls ProcessComm and bench.py make -- id hand-over from rank 0, barriers, gather of per-rank objects, max over the clocks --
 and a stale socket name left behind by an earlier (crashed) job."""
 import os
+import pathlib
+import shutil
 import socket
 import subprocess
 import sys
+import tempfile
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture
+def sock_dir():
+    """TMPDIR of the ranks: their socket names are made under it, and a Unix socket's path must fit in 107 bytes -- pytest's tmp_path under a
+    long base directory does not."""
+    d = tempfile.mkdtemp(prefix="ctl_", dir="/tmp")
+    try:
+        yield pathlib.Path(d)
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
 WORKER = r'''
 import os, sys, time
 sys.path.insert(0, %(root)r)
@@ -30,14 +48,14 @@ print("rank %%d ok" %% rank)
 '''
 
 
-def test_local_control_world3(tmp_path):
+def test_local_control_world3(tmp_path, sock_dir):
     script = tmp_path / "w.py"
     script.write_text(WORKER % dict(root=ROOT))
-    env = dict(os.environ, MASTER_PORT="29643", TORCHELASTIC_RUN_ID="t1", TMPDIR=str(tmp_path))
+    env = dict(os.environ, MASTER_PORT="29643", TORCHELASTIC_RUN_ID="t1", TMPDIR=str(sock_dir))
     sys.path.insert(0, ROOT)
     from ccv_amd import ctl
     old = dict(os.environ)
-    os.environ.update(MASTER_PORT="29643", TORCHELASTIC_RUN_ID="t1", TMPDIR=str(tmp_path))
+    os.environ.update(MASTER_PORT="29643", TORCHELASTIC_RUN_ID="t1", TMPDIR=str(sock_dir))
     try:
         stale = ctl.default_path()
     finally:
@@ -73,28 +91,28 @@ time.sleep(600)              # stands for a rank inside an RCCL collective the d
 '''
 
 
-def _run_dying(tmp_path, dies, port):
+def _run_dying(tmp_path, sock_dir, dies, port):
     import time
     script = tmp_path / "d.py"
     script.write_text(DYING % dict(root=ROOT))
-    env = dict(os.environ, MASTER_PORT=port, TORCHELASTIC_RUN_ID="t2", TMPDIR=str(tmp_path), DIES=str(dies))
+    env = dict(os.environ, MASTER_PORT=port, TORCHELASTIC_RUN_ID="t2", TMPDIR=str(sock_dir), DIES=str(dies))
     t0 = time.time()
     procs = [subprocess.Popen([sys.executable, str(script)], env=dict(env, RANK=str(r), WORLD_SIZE="3", LOCAL_RANK=str(r)), stderr=subprocess.PIPE, text=True) for r in range(3)]
     errs = [p.communicate(timeout=60)[1] for p in procs]
     return [p.returncode for p in procs], errs, time.time() - t0
 
 
-def test_a_dead_rank_takes_the_job_down_instead_of_hanging_it(tmp_path):
+def test_a_dead_rank_takes_the_job_down_instead_of_hanging_it(tmp_path, sock_dir):
     """Round 5: a rank that dies mid-job leaves its peers in a collective that never completes.  The liveness star + watchdog ends
     every surviving rank within seconds (exit code 70): rank 0 sees rank 2 go, the others see rank 0 go."""
-    codes, errs, dt = _run_dying(tmp_path, 2, "29644")
+    codes, errs, dt = _run_dying(tmp_path, sock_dir, 2, "29644")
     assert codes == [70, 70, 9] and dt < 30, (codes, errs, dt)
     assert "went away" in errs[0]
-    codes, errs, dt = _run_dying(tmp_path, 0, "29645")
+    codes, errs, dt = _run_dying(tmp_path, sock_dir, 0, "29645")
     assert codes == [9, 70, 70] and dt < 30, (codes, errs, dt)
 
 
-def test_the_job_deadline_stops_a_stuck_rank(tmp_path):
+def test_the_job_deadline_stops_a_stuck_rank(tmp_path, sock_dir):
     script = tmp_path / "s.py"
     script.write_text(r'''
 import os, sys, time
@@ -104,7 +122,7 @@ c = LocalControl(int(os.environ["RANK"]), 2, timeout=60, deadline_s=2.0)
 c.barrier()
 time.sleep(600)
 ''' % ROOT)
-    env = dict(os.environ, MASTER_PORT="29646", TORCHELASTIC_RUN_ID="t3", TMPDIR=str(tmp_path))
+    env = dict(os.environ, MASTER_PORT="29646", TORCHELASTIC_RUN_ID="t3", TMPDIR=str(sock_dir))
     procs = [subprocess.Popen([sys.executable, str(script)], env=dict(env, RANK=str(r), WORLD_SIZE="2"), stderr=subprocess.PIPE, text=True) for r in range(2)]
     errs = [p.communicate(timeout=60)[1] for p in procs]
     assert sorted(p.returncode for p in procs)[-1] == 71 and all(p.returncode in (70, 71) for p in procs), ([p.returncode for p in procs], errs)
@@ -125,7 +143,7 @@ c.destroy_process_group()
 '''
 
 
-def test_a_rank_that_exits_normally_is_not_a_death_and_there_is_no_default_deadline(tmp_path):
+def test_a_rank_that_exits_normally_is_not_a_death_and_there_is_no_default_deadline(tmp_path, sock_dir):
     """(a) a rank that finishes and leaves the interpreter without destroy_process_group() says goodbye from an atexit hook -- its peers
     keep running (they used to stop with exit code 70); (b) the job deadline is off unless asked for (it defaulted to 3000 s and killed healthy long jobs)."""
     import time
@@ -134,7 +152,7 @@ def test_a_rank_that_exits_normally_is_not_a_death_and_there_is_no_default_deadl
     assert '"NNC_MI355X_CTL_DEADLINE_S", "0"' in inspect.getsource(ctl.LocalControl.__init__)
     script = tmp_path / "g.py"
     script.write_text(GOING % dict(root=ROOT))
-    env = dict(os.environ, MASTER_PORT="29661", TORCHELASTIC_RUN_ID="t4", TMPDIR=str(tmp_path))
+    env = dict(os.environ, MASTER_PORT="29661", TORCHELASTIC_RUN_ID="t4", TMPDIR=str(sock_dir))
     env.pop("NNC_MI355X_CTL_DEADLINE_S", None)
     procs = [subprocess.Popen([sys.executable, str(script)], env=dict(env, RANK=str(r), WORLD_SIZE="3", LOCAL_RANK=str(r)), stderr=subprocess.PIPE, text=True) for r in range(3)]
     errs = [p.communicate(timeout=60)[1] for p in procs]

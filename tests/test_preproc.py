@@ -151,7 +151,7 @@ def test_resample_area_8u_extremes_bit_exact(backend, classic, shape, out, fill)
 
 
 @pytest.mark.gpu
-def test_resample_area_8u_imagenet_size_bit_exact(gpu_lib):
+def test_resample_area_8u_imagenet_size_bit_exact(gpu_lib, tmp_path):
     """256 x 480 x 480 x 3 -> 224 x 224 (the size the bench quotes) on the MI355X, every image against the numpy restatement of ccv_resample's 8-bit area path
     (oracle/preproc_oracle.py, pinned to libccv_classic.so by the tests above), and the old one-lane-per-byte kernel against the new one."""
     import subprocess
@@ -163,8 +163,7 @@ def test_resample_area_8u_imagenet_size_bit_exact(gpu_lib):
     for g, a in zip(got[:3], imgs[:3]):
         np.testing.assert_array_equal(g, PO.resample_area_8u(a, 224, 224, rs, cs))
     code = "import sys, numpy as np; sys.path.insert(0, %r); sys.path.insert(0, %r); import test_preproc as T; from ccv_amd import nnc; rng = np.random.default_rng(5); imgs = [rng.integers(0, 256, (480, 480, 3), dtype=np.uint8) for _ in range(8)]; got = T.our_resample(nnc.load(), imgs, (224, 224), np.uint8, 224 / 480, 224 / 480, T.AREA); np.save(sys.argv[1], np.stack(got))" % (ROOT, os.path.join(ROOT, "tests"))
-    path = os.path.join(ROOT, "gpurun_out", "resample_old_kernel.npy")
-    os.makedirs(os.path.dirname(path), exist_ok=True)
+    path = str(tmp_path / "resample_old_kernel.npy")
     r = subprocess.run([sys.executable, "-c", code, path], capture_output=True, text=True, timeout=600, env=dict(os.environ, NNC_MI355X_RESAMPLE_ROWS="0"))
     assert r.returncode == 0, r.stderr[-2000:]
     np.testing.assert_array_equal(np.load(path), np.stack(got))

@@ -18,6 +18,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 STEPS=${STEPS:-6}
+BENCH_ARGS="--full ${BENCH_ARGS}"  # bench / config:<name> record everything beyond the headline (records, roofline, CPU baseline, extra configs)
 prof_cmd() { # $1 = tag, rest = command
   tag=$1; shift
   rm -rf gpurun_out/prof_$tag
