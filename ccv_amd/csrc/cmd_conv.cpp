@@ -31,6 +31,25 @@ static bool mask_fits(const Image4& dst)
 	return m.p && m.n == dst.n && m.h == dst.h && m.w == dst.w && m.c == dst.c && m.sc == 1 && aligned16(m.p) && m.sw % 4 == 0 && m.sh % 4 == 0 && (m.n == 1 || m.sn % 4 == 0);
 }
 
+// A backward command that computes BOTH gradients (_conv_back) runs its filter gradient first.  Where a pass of the filter gradient reads a tensor that a
+// kernel of the data gradient would read again, it makes that kernel's product on the way and leaves it in the command's workspace, behind everything the
+// filter gradient itself uses (TUNE_CONV_BACK_SHARE; same expressions in the same order: bit-identical).  Lives for ONE command: _conv_back sets the wishes
+// from what the data gradient WILL run, conv_wino_wgrad fills in what it made, the data gradient's launcher takes it if it is there, _conv_back clears.
+struct back_share_t {
+	int want_v;         // the data gradient is conv_wino_run<true> on the filter gradient's tile grid, unsliced: its V = B^T g B can come from the pass that makes W = G' g G'^T
+	int want_bits;      // the data gradient is the fused kernel with 2 x 8 tile groups under a ReLU mask, the mask being the map the filter gradient transforms
+	int GYn, GXn, KB;   // want_bits: that kernel's tile groups per image and 32-channel blocks
+	float* v;           // made: V, at v_off bytes into the workspace (whatever lies in front of it is free once the filter gradient is done)
+	unsigned* bits;     // made: the mask bits in wino_mask_pack_kernel<2, 8>'s layout, at bits_off
+	size_t v_off, bits_off;
+};
+static thread_local back_share_t tl_share = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+
+// nnc_mi355x_debug_conv_mask_bits (tests): host memory that the next fused masked data gradient copies its mask bits to, whoever made them
+static void* g_dbg_bits_dst = 0;
+static size_t g_dbg_bits_cap = 0, g_dbg_bits_got = 0;
+static long g_back_shared[2] = { 0, 0 }; // nnc_mi355x_debug_conv_back_shared: launches of wino_outgrad_both_kernel / wino_input_kernel<true>
+
 struct conv_geom_t {
 	int N, H, W, C;     // input
 	int OH, OW, K;      // output
@@ -127,11 +146,16 @@ static int conv_wino_run(const char* name, const conv_geom_t& g, const wino_plan
 	const int nb = wino_slice_images(g.N, per_image, Cs, Cd);
 	const size_t v_bytes = nb == g.N ? p.v_bytes : (sizeof(float) * 36 * (size_t)nb * per_image * Cs + 255) & ~(size_t)255;
 	const size_t m_bytes = nb == g.N ? p.m_bytes : (sizeof(float) * 36 * (size_t)nb * per_image * Cd + 255) & ~(size_t)255;
-	char* ws = (char*)workspace_of(ctx, p.u_bytes + v_bytes + m_bytes);
+	// (data gradient behind the same command's filter gradient: V is already there -- wino_outgrad_both_kernel -- and U, M go in front of it)
+	bool have_v = FLIP && tl_share.v && nb == g.N && p.u_bytes + m_bytes <= tl_share.v_off;
+	size_t need = p.u_bytes + v_bytes + m_bytes;
+	if (have_v && tl_share.v_off + v_bytes > need) need = tl_share.v_off + v_bytes;
+	char* ws = (char*)workspace_of(ctx, need);
 	if (!ws) return CCV_NNC_EXEC_OOM;
+	if (have_v && (float*)(ws + tl_share.v_off) != tl_share.v) have_v = false; // (the workspace moved: not inside a scope)
 	float* const U = (float*)ws;
-	float* const V = (float*)(ws + p.u_bytes);
-	float* const M = (float*)(ws + p.u_bytes + v_bytes);
+	float* const V = have_v ? tl_share.v : (float*)(ws + p.u_bytes);
+	float* const M = have_v ? (float*)(ws + p.u_bytes) : (float*)(ws + p.u_bytes + v_bytes);
 	hipStream_t stream = stream_of(ctx);
 	hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_weight_kernel<FLIP>), dim3(blocks_exact((size_t)Cs * Cd, 256)), dim3(256), 0, stream, w, U, g.K, g.C);
 	HIP_ENFORCE(hipGetLastError());
@@ -145,7 +169,7 @@ static int conv_wino_run(const char* name, const conv_geom_t& g, const wino_plan
 		if (ti.relu) tl_relu_done = 1;
 		ti.mask = 0; ti.m_sn = ti.m_sh = ti.m_sw = 0;
 		ti.d_c4.init(ti.C4); ti.d_tw.init(ti.TW); ti.d_th.init(ti.TH);
-		hipLaunchKernelGGL(wino_input_kernel, dim3(blocks_exact((size_t)T * ti.C4, 256)), dim3(256), 0, stream, (const float*)src.p + (long)n0 * src.sn, V, ti);
+		if (!have_v) hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_input_kernel<false>), dim3(blocks_exact((size_t)T * ti.C4, 256)), dim3(256), 0, stream, (const float*)src.p + (long)n0 * src.sn, V, ti, WinoMaskOut());
 		HIP_ENFORCE(hipGetLastError());
 		// 36 GEMMs M[z] (T x Cd) = V[z] (T x Cs) * U[z]^T (Cd x Cs), both operands reduction-contiguous, one launch (grid z)
 		MatLoader<true, true> la, lb;
@@ -221,12 +245,16 @@ static int conv_wino_fused_run(const char* name, const conv_geom_t& g, const win
 {
 	// data gradient under a ReLU backward: the mask as bits in the epilogue's order, packed first (1 / 32 of the map; no room: unmasked, the caller's pass follows)
 	size_t bits_bytes = FLIP && mask_fits(dst) && (long)p.groups * p.KB <= 0x7fffffffL ? (size_t)p.groups * p.KB * 1024 : 0;
-	float* UF = (float*)workspace_of(ctx, p.uf_bytes + bits_bytes);
+	// (behind the same command's filter gradient the bits may be there already: wino_input_kernel<true> wrote them next to V)
+	bool have_bits = FLIP && bits_bytes && tl_share.bits && p.GH == 2 && p.GYn == tl_share.GYn && p.GXn == tl_share.GXn && p.KB == tl_share.KB && p.uf_bytes <= tl_share.bits_off;
+	float* UF = (float*)workspace_of(ctx, have_bits ? tl_share.bits_off + bits_bytes : p.uf_bytes + bits_bytes);
+	if (have_bits && (!UF || (unsigned*)((char*)UF + tl_share.bits_off) != tl_share.bits)) { have_bits = false; UF = (float*)workspace_of(ctx, p.uf_bytes + bits_bytes); }
 	if (!UF && bits_bytes) { bits_bytes = 0; UF = (float*)workspace_of(ctx, p.uf_bytes); }
 	if (!UF) return CCV_NNC_EXEC_OOM;
 	hipStream_t stream = stream_of(ctx);
-	unsigned* const bits = bits_bytes ? (unsigned*)((char*)UF + p.uf_bytes) : 0;
-	if (bits) {
+	unsigned* const bits = have_bits ? tl_share.bits : (bits_bytes ? (unsigned*)((char*)UF + p.uf_bytes) : 0);
+	if (have_bits) tl_mask_done = 1;
+	else if (bits) {
 		const dim3 grid((unsigned)((long)p.groups * p.KB));
 		const Image4& m = tl_mask;
 		if (p.GH == 4) hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_mask_pack_kernel<4, 4>), grid, dim3(256), 0, stream, (const float*)m.p, m.sn, m.sh, m.sw, bits, dst.h, dst.w, dst.c, p.GYn, p.GXn, p.KB);
@@ -234,6 +262,12 @@ static int conv_wino_fused_run(const char* name, const conv_geom_t& g, const win
 		else hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_mask_pack_kernel<8, 2>), grid, dim3(256), 0, stream, (const float*)m.p, m.sn, m.sh, m.sw, bits, dst.h, dst.w, dst.c, p.GYn, p.GXn, p.KB);
 		HIP_ENFORCE(hipGetLastError());
 		tl_mask_done = 1;
+	}
+	if (bits && g_dbg_bits_dst) {
+		g_dbg_bits_got = (size_t)p.groups * p.KB * 1024;
+		HIP_ENFORCE(hipMemcpyAsync(g_dbg_bits_dst, bits, g_dbg_bits_got < g_dbg_bits_cap ? g_dbg_bits_got : g_dbg_bits_cap, hipMemcpyDeviceToHost, stream));
+		HIP_ENFORCE(hipStreamSynchronize(stream));
+		g_dbg_bits_dst = 0;
 	}
 	const int Kout = dst.c, Cred = src.c;
 	hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_weight_frag_kernel<FLIP>), dim3(blocks_exact((size_t)p.KB * WF_KT * Cred, 256)), dim3(256), 0, stream, w, UF, Kout, Cred, g.K, g.C);
@@ -329,17 +363,26 @@ static int conv_wino_wgrad(const conv_geom_t& g, const wino_wgrad_plan_t& p, con
 {
 	// [ head: nested calls' scratch (they take the workspace base) | V | W | dU | per-block column sums ]
 	// (sized for the whole batch: a slice -- TUNE_WINO_SLICE_KB -- uses the front of each region)
-	char* ws = (char*)workspace_of(ctx, p.total());
+	// [ ... | the data gradient's V or mask bits ]: what this command's data gradient finds ready (tl_share; only unsliced, so ONE pass below makes all of it)
+	const int per_image = p.t.TH * p.t.TW;
+	const int nb = wino_slice_images(g.N, per_image, g.C, g.K);
+	const size_t bits_bytes = (size_t)g.N * tl_share.GYn * tl_share.GXn * tl_share.KB * 1024;
+	const bool fuse_bias = dbias && 256 % (g.K / 4) == 0;
+	const size_t extra = nb != g.N ? 0 : (tl_share.want_v ? (fuse_bias ? p.w_bytes : 0) : (tl_share.want_bits ? bits_bytes : 0)); // (the one-pass kernel exists with the bias sums only: winograd.h)
+	char* ws = (char*)workspace_of(ctx, p.total() + extra);
 	if (!ws) return CCV_NNC_EXEC_OOM;
+	float* const Vg = extra && tl_share.want_v ? (float*)(ws + p.total()) : 0; // as large as W: 36 x T x K
+	unsigned* const bits = extra && tl_share.want_bits ? (unsigned*)(ws + p.total()) : 0;
 	float* const V = (float*)(ws + p.head_bytes);
 	float* const W = (float*)(ws + p.head_bytes + p.t.v_bytes);
 	float* const dU = (float*)(ws + p.head_bytes + p.t.v_bytes + p.w_bytes);
 	float* const BP = (float*)(ws + p.head_bytes + p.t.v_bytes + p.w_bytes + p.du_bytes);
-	const bool fuse_bias = dbias && 256 % (g.K / 4) == 0;
 	const int acc = (flags & CCV_NNC_ACCUMULATE_OUTPUT) ? 1 : 0;
 	hipStream_t stream = stream_of(ctx);
-	const int per_image = p.t.TH * p.t.TW;
-	const int nb = wino_slice_images(g.N, per_image, g.C, g.K);
+	if (bits && (tl_share.GYn * 2 != p.t.TH || tl_share.GXn * 8 != p.t.TW || g.C % WF_KT)) { // tile groups beyond the tile grid, channels beyond C: zeros, and no thread below owns them
+		const int r = fill_f32((float*)bits, bits_bytes / sizeof(float), 0.f, ctx);
+		if (r != CCV_NNC_EXEC_SUCCESS) return r;
+	}
 	for (int n0 = 0; n0 < g.N; n0 += nb) {
 		const int ns = g.N - n0 < nb ? g.N - n0 : nb;
 		const int T = ns * per_image;
@@ -347,13 +390,24 @@ static int conv_wino_wgrad(const conv_geom_t& g, const wino_wgrad_plan_t& p, con
 		ti.TH = p.t.TH; ti.TW = p.t.TW; ti.T = T;
 		ti.H = a.h; ti.W = a.w; ti.sn = a.sn; ti.sh = a.sh; ti.sw = a.sw; ti.oy = -g.pby; ti.ox = -g.pbx; ti.C4 = g.C / 4;
 		ti.d_c4.init(ti.C4); ti.d_tw.init(ti.TW); ti.d_th.init(ti.TH);
-		hipLaunchKernelGGL(wino_input_kernel, dim3(blocks_exact((size_t)T * ti.C4, 256)), dim3(256), 0, stream, (const float*)a.p + (long)n0 * a.sn, V, ti);
+		if (bits) { // (padding 1: the 4x4 pixels of tile t are the middle of its patch)
+			WinoMaskOut mo;
+			mo.bits = (unsigned char*)bits; mo.GYn = tl_share.GYn; mo.GXn = tl_share.GXn; mo.KB = tl_share.KB;
+			hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_input_kernel<true>), dim3(blocks_exact((size_t)T * ti.C4, 256)), dim3(256), 0, stream, (const float*)a.p + (long)n0 * a.sn, V, ti, mo);
+			tl_share.bits = bits; tl_share.bits_off = p.total();
+			__atomic_fetch_add(&g_back_shared[1], 1L, __ATOMIC_RELAXED);
+		} else hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_input_kernel<false>), dim3(blocks_exact((size_t)T * ti.C4, 256)), dim3(256), 0, stream, (const float*)a.p + (long)n0 * a.sn, V, ti, WinoMaskOut());
 		HIP_ENFORCE(hipGetLastError());
 		ti.H = gr.h; ti.W = gr.w; ti.sn = gr.sn; ti.sh = gr.sh; ti.sw = gr.sw; ti.oy = 0; ti.ox = 0; ti.C4 = g.K / 4;
 		ti.d_c4.init(ti.C4);
 		const long blocks = ((long)T * (g.K / 4) + 255) / 256;
 		const float* const grs = (const float*)gr.p + (long)n0 * gr.sn;
-		if (fuse_bias) hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_outgrad_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, stream, grs, W, ti, BP);
+		if (Vg) { // one pass over the gradient for both of its transforms (the data gradient's patch of tile t starts one pixel up and left of the tile)
+			ti.oy = -1; ti.ox = -1;
+			hipLaunchKernelGGL(wino_outgrad_both_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, grs, Vg, W, ti, BP);
+			tl_share.v = Vg; tl_share.v_off = p.total();
+			__atomic_fetch_add(&g_back_shared[0], 1L, __ATOMIC_RELAXED);
+		} else if (fuse_bias) hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_outgrad_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, stream, grs, W, ti, BP);
 		else hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_outgrad_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, stream, grs, W, ti, (float*)0);
 		HIP_ENFORCE(hipGetLastError());
 		MatLoader<false, true> la, lb; // rows = channels (contiguous), reduction index = tile (stride = channel count)
@@ -659,16 +713,26 @@ static int conv_dgrad_parity(const conv_geom_t& g, const Image4& gr, const float
 	return CCV_NNC_EXEC_SUCCESS;
 }
 
+// which Winograd form the data gradient takes first (conv_dgrad_nhwc; _conv_back asks ahead of the filter gradient: tl_share)
+static bool conv_dgrad_takes_fused(const conv_geom_t& g, const Image4& gr, const Image4& h, const int algo, wino_fused_plan_t* fp)
+{
+	return algo != CONV_ALGO_IMPLICIT_GEMM && algo != CONV_ALGO_WINOGRAD && g.pby <= 2 && g.pbx <= 2 && g.pby >= 0 && g.pbx >= 0 && wino_fused_plan(g, gr, h, fp) && (algo == CONV_ALGO_WINOGRAD_FUSED || wino_fused_preferred(g.K, *fp, h));
+}
+static bool conv_dgrad_takes_wino(const conv_geom_t& g, const Image4& gr, const float* w, const Image4& h, const int algo, wino_plan_t* wp)
+{
+	return algo != CONV_ALGO_IMPLICIT_GEMM && wino_plan(g, g.H, g.W, g.K, g.C, wp) && wino_images_ok(gr, h, w, 0) && (algo >= CONV_ALGO_WINOGRAD || wino_preferred(*wp, g.K, g.C));
+}
+
 static int conv_dgrad_nhwc(const conv_geom_t& g, const Image4& gr, const float* w, const Image4& h, const int algo, const int flags, ccv_nnc_stream_context_t* const ctx)
 {
 	if (gr.sc != 1 || !pixel_linear(h) || !image_fits_int(gr)) return CCV_NNC_EXEC_INVALID;
 	wino_plan_t wp;
 	wino_fused_plan_t fp;
-	if (algo != CONV_ALGO_IMPLICIT_GEMM && algo != CONV_ALGO_WINOGRAD && g.pby <= 2 && g.pbx <= 2 && g.pby >= 0 && g.pbx >= 0 && wino_fused_plan(g, gr, h, &fp) && (algo == CONV_ALGO_WINOGRAD_FUSED || wino_fused_preferred(g.K, fp, h))) {
+	if (conv_dgrad_takes_fused(g, gr, h, algo, &fp)) {
 		const int r = conv_wino_fused_run<true>("conv_dgrad_wino_fused", g, fp, gr, w, 0, h, 2 - g.pby, 2 - g.pbx, ctx);
 		if (r != CCV_NNC_EXEC_OOM) return r;
 	}
-	if (algo != CONV_ALGO_IMPLICIT_GEMM && wino_plan(g, g.H, g.W, g.K, g.C, &wp) && wino_images_ok(gr, h, w, 0) && (algo >= CONV_ALGO_WINOGRAD || wino_preferred(wp, g.K, g.C))) {
+	if (conv_dgrad_takes_wino(g, gr, w, h, algo, &wp)) {
 		const int r = conv_wino_run<true>("conv_dgrad_wino", g, wp, gr, w, 0, h, 2 - g.pby, 2 - g.pbx, flags, ctx);
 		if (r != CCV_NNC_EXEC_OOM) return r;
 	}
@@ -704,6 +768,18 @@ static int conv_dgrad_nhwc(const conv_geom_t& g, const Image4& gr, const float* 
 #undef CONV_DGRAD
 }
 
+// which Winograd form the filter gradient takes (conv_wgrad_nhwc, behind the 3-channel kernel)
+// (algorithm 2 = "the fused kernels" takes the fused filter gradient under the same rule as algorithm -1: the host's autotuner times the WHOLE backward
+// command per algorithm, and a 256-channel layer wants the fused data gradient next to the via-HBM filter gradient)
+static bool conv_wgrad_takes_fused(const conv_geom_t& g, const Image4& gr, const Image4& a, const float* dw, const int algo, wino_wgrad_fused_plan_t* wfp)
+{
+	return algo != CONV_ALGO_IMPLICIT_GEMM && algo != CONV_ALGO_WINOGRAD && wino_wgrad_fused_plan(g, wfp) && wino_wgrad_fused_images_ok(a, gr, dw) && wino_wgrad_fused_preferred(g);
+}
+static bool conv_wgrad_takes_wino(const conv_geom_t& g, const Image4& gr, const Image4& a, const float* dw, const int algo, wino_wgrad_plan_t* wp)
+{
+	return algo != CONV_ALGO_IMPLICIT_GEMM && wino_wgrad_plan(g, wp) && wino_images_ok(a, gr, dw, 0) && (algo >= CONV_ALGO_WINOGRAD || wino_preferred(wp->t, g.C, g.K));
+}
+
 // dw[k,i,j,c] (+)= sum_{n,y,x} g[n,y,x,k] * a[n, y*s-p+i*d, x*s-p+j*d, c]
 static int conv_wgrad_nhwc(const conv_geom_t& g, const Image4& gr, const Image4& a, float* dw, float* dbias, bool* bias_done, const int algo, const int flags, ccv_nnc_stream_context_t* const ctx)
 {
@@ -715,14 +791,12 @@ static int conv_wgrad_nhwc(const conv_geom_t& g, const Image4& gr, const Image4&
 		if (r != CCV_NNC_EXEC_OOM) return r;
 	}
 	wino_wgrad_fused_plan_t wfp;
-	// (algorithm 2 = "the fused kernels" takes the fused filter gradient under the same rule as algorithm -1: the host's autotuner times the WHOLE backward
-	// command per algorithm, and a 256-channel layer wants the fused data gradient next to the via-HBM filter gradient)
-	if (algo != CONV_ALGO_IMPLICIT_GEMM && algo != CONV_ALGO_WINOGRAD && wino_wgrad_fused_plan(g, &wfp) && wino_wgrad_fused_images_ok(a, gr, dw) && wino_wgrad_fused_preferred(g)) {
+	if (conv_wgrad_takes_fused(g, gr, a, dw, algo, &wfp)) {
 		const int r = conv_wino_wgrad_fused(g, wfp, gr, a, dw, dbias, bias_done, flags, ctx);
 		if (r != CCV_NNC_EXEC_OOM) return r;
 	}
 	wino_wgrad_plan_t wp;
-	if (algo != CONV_ALGO_IMPLICIT_GEMM && wino_wgrad_plan(g, &wp) && wino_images_ok(a, gr, dw, 0) && (algo >= CONV_ALGO_WINOGRAD || wino_preferred(wp.t, g.C, g.K))) {
+	if (conv_wgrad_takes_wino(g, gr, a, dw, algo, &wp)) {
 		const int r = conv_wino_wgrad(g, wp, gr, a, dw, dbias, bias_done, flags, ctx);
 		if (r != CCV_NNC_EXEC_OOM) return r;
 	}
@@ -966,6 +1040,32 @@ static int _conv_back(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const 
 	if (h && cmd.algorithm != CONV_ALGO_IMPLICIT_GEMM && wino_fused_scratch_bound(g.C, g.K) + wino_fused_mask_bound(g) > inner) inner = wino_fused_scratch_bound(g.C, g.K) + wino_fused_mask_bound(g);
 	if (h && cmd.algorithm != CONV_ALGO_IMPLICIT_GEMM && conv_dgrad_parity_scratch(g) > inner) inner = conv_dgrad_parity_scratch(g);
 	if (dw && cmd.algorithm != CONV_ALGO_IMPLICIT_GEMM && g.C == 3 && conv_c3_wgrad_scratch_bound(g.K) > inner) inner = conv_c3_wgrad_scratch_bound(g.K);
+	// Both gradients on the tensors where they lie, the filter gradient via HBM, padding 1 (the 4x4 tiles of the output gradient and of a are the middles of
+	// the data gradient's / the filter gradient's 6x6 patches, on one tile grid), no image slices: what the data gradient needs of a tensor the filter gradient
+	// reads anyway is made in that pass (tl_share) and kept behind the filter gradient's scratch.
+	back_share_t share = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+	const long share_on = tune(TUNE_CONV_BACK_SHARE);
+	if (h && dw && a && w && share_on && !stage_io && !stage_w && g.pby == 1 && g.pbx == 1 && g.OH == g.H && g.OW == g.W && ai.sc == 1 && gi.sc == 1 && pixel_linear(gi) && pixel_linear(hi) && image_fits_int(ai) && image_fits_int(gi)
+		&& !(cmd.algorithm != CONV_ALGO_IMPLICIT_GEMM && conv_c3_ok(g, ai, gi))) {
+		wino_wgrad_fused_plan_t wf;
+		wino_wgrad_plan_t wg;
+		wino_fused_plan_t fp;
+		wino_plan_t wp;
+		if (!conv_wgrad_takes_fused(g, gi, ai, dw->data.f32, cmd.algorithm, &wf) && conv_wgrad_takes_wino(g, gi, ai, dw->data.f32, cmd.algorithm, &wg) && wino_slice_images(g.N, wg.t.TH * wg.t.TW, g.C, g.K) == g.N) {
+			if (conv_dgrad_takes_fused(g, gi, hi, cmd.algorithm, &fp)) {
+				tl_mask = ai; // (as below, for mask_fits)
+				if ((share_on & 2) && tl_mask_want && fp.GH == 2 && mask_fits(hi) && (long)fp.groups * fp.KB <= 0x7fffffffL && fp.uf_bytes <= wg.total()) {
+					share.want_bits = 1; share.GYn = fp.GYn; share.GXn = fp.GXn; share.KB = fp.KB;
+					if (wg.total() + (size_t)fp.groups * fp.KB * 1024 > inner) inner = wg.total() + (size_t)fp.groups * fp.KB * 1024;
+				}
+				tl_mask.p = 0;
+			} else if ((share_on & 1) && dbias && 256 % (g.K / 4) == 0 && conv_dgrad_takes_wino(g, gi, w->data.f32, hi, cmd.algorithm, &wp) && wp.TH == wg.t.TH && wp.TW == wg.t.TW && wp.u_bytes + wp.m_bytes <= wg.total()) {
+				share.want_v = 1;
+				if (wg.total() + wg.w_bytes > inner) inner = wg.total() + wg.w_bytes;
+			}
+		}
+	}
+	struct share_scope_t { share_scope_t(const back_share_t& s) { tl_share = s; } ~share_scope_t() { const back_share_t none = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }; tl_share = none; } } share_scope(share);
 	WorkspaceScope ws(stream_context, ng + na + nh + nw + ndw, inner);
 	char* p = (char*)ws.prefix();
 	if ((ng + na + nh + nw + ndw) && !p) return CCV_NNC_EXEC_OOM;
@@ -1531,6 +1631,13 @@ static int _conv_autotune(const ccv_nnc_cmd_t cmd, const size_t max_workspace_si
 }
 
 } // namespace
+
+extern "C" long nnc_mi355x_debug_conv_back_shared(int what) { return what == 0 || what == 1 ? __atomic_load_n(&g_back_shared[what], __ATOMIC_RELAXED) : 0; }
+extern "C" size_t nnc_mi355x_debug_conv_mask_bits(void* dst, size_t capacity)
+{
+	g_dbg_bits_dst = dst; g_dbg_bits_cap = capacity;
+	return g_dbg_bits_got;
+}
 
 extern "C" void _register_command_CCV_NNC_CONVOLUTION_FORWARD_backend_CCV_NNC_BACKEND_GPU_CUDNN(ccv_nnc_cmd_backend_registry_t* const registry)
 {

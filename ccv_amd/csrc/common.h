@@ -254,6 +254,7 @@ enum {
 	TUNE_GEMM_BF16X3,       // fp32 plain-matrix contractions on the bf16 matrix pipe, every operand split exactly into three bf16 values and all nine partial products accumulated in fp32 (mfma_gemm_bf16x3.h): 0 = never (the fp32 matrix instructions), 1 = where the launcher's rules say it pays, 2 = wherever the kernel applies, 3 / 4 = as 2 with the 128 x 128 / 256 x 256 tile forced (measurements)
 	TUNE_BN_CLUSTER_SLOTS,  // the cluster batch-norm kernels on tensors too small to fill the chip with full workgroup shares: shares are cut down until the launch has about this many workgroups (never below two chunks per thread); 0 = always the largest share a workgroup's registers hold (rounds 4 - 5)
 	TUNE_GEMM_BATCH_XCD,    // batched contractions without split-K (a 1 x 1 convolution on NCHW tensors: one matrix product per image) launch ONE grid dimension over (entry, tile) and give every batch entry to one XCD: the tiles of an entry meet in ONE L2, so its B operand -- the image's planes, which every row block of the output reads -- leaves HBM once, not once per XCD (1); 0 = entries on grid z, tiles dealt round-robin over the XCDs (rounds 1 - 5)
+	TUNE_CONV_BACK_SHARE,   // a backward convolution that computes both gradients reads a tensor ONCE where two of its kernels read the same one: bit 0 = the output gradient's two Winograd transforms (data gradient V, filter gradient W, bias sums) in one kernel, bit 1 = the fused data gradient's ReLU mask bits written by the filter gradient's input transform; 0 = the separate kernels (rounds 1 - 6; the results are bit for bit the same)
 	TUNE_COUNT
 };
 static_assert(TUNE_GRID_WG_PER_CU == 3, "grid_for() above names this key by value");

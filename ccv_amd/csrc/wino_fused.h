@@ -664,7 +664,8 @@ __global__ void __launch_bounds__(256) wino_mask_pack_kernel(const float* __rest
 {
 	constexpr int GWL = GW == 4 ? 2 : (GW == 8 ? 3 : (GW == 2 ? 1 : (GW == 16 ? 4 : 0)));
 	static_assert(GH * GW == 16, "16 tiles per group");
-	int b = (int)blockIdx.x;
+	static_assert(WF_KT == WINO_MASK_KT, "winograd.h describes this layout");
+	int b = (int)blockIdx.x; // = wino_mask_item(n, gy, gx, kb, GYn, GXn, KB)
 	const int kb = b % KB; b /= KB;
 	const int gx = b % GXn; b /= GXn;
 	const int gy = b % GYn;
@@ -675,9 +676,8 @@ __global__ void __launch_bounds__(256) wino_mask_pack_kernel(const float* __rest
 	unsigned m = 0;
 #pragma unroll
 	for (int e = 0; e < 8; e++) {
-		const int pid = e * 8 + (lane >> 3);
-		const int gp = pid >> 4, px = pid & 15;
-		const int tile = 4 * gp + r;
+		const int pid = wino_mask_pid(e, lane), px = pid & 15;
+		const int tile = wino_mask_tile(pid, r);
 		const int oy = (gy * GH + (tile >> GWL)) * 4 + (px >> 2), ox = (gx * GW + (tile & (GW - 1))) * 4 + (px & 3);
 		if ((kq < K) & (oy < OH) & (ox < OW)) {
 			const float4 v = *(const float4*)(mp + (long)oy * m_sh + (long)ox * m_sw);

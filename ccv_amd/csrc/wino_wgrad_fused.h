@@ -61,7 +61,8 @@ __global__ void __launch_bounds__(256, 1) wino_wgrad_fused_kernel(const WinoWgra
 {
 	__shared__ __attribute__((aligned(16))) float lds[2 * WG_STAGE_BYTES / 4 + 256]; // two stages + 1 KB where the empty issue slots (waves 1 - 3 have 11 input pieces, not 12) drop their zeros
 	const int t = threadIdx.x, lane = t & 63;
-	const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+	const int wave = __builtin_amdgcn_readfirstlane(t >> 6) & 3; // (& 3: four waves, which hipcc cannot see behind the intrinsic -- without it every `wave + 4 i < WG_A_PIECES` below is a run-time condition,
+	                                                              // kept as a lane mask in spilled SGPRs and BRANCHED on in the MFMA stream, seven times per trip)
 	const int wk = wave >> 1, wc = wave & 1;
 	const int ch = lane & 15, slot = lane >> 4;
 	// workgroup -> (slice, k block, c block): the blocks of one slice read the same regions, so they sit on ONE XCD (workgroup b runs on XCD b % 8)

@@ -134,9 +134,32 @@ struct WinoTiles {
 	FastDiv d_c4, d_tw, d_th;
 };
 
+// ---- layout of the fused data gradient's ReLU mask bits (wino_fused.h: WinoFusedArgs::mask_bits, written by wino_mask_pack_kernel or by
+// wino_input_kernel<true> below).  An item = one GH x GW group of 16 tiles x one block of 32 channels, items in (n, gy, gx, kb) order, 256 dwords
+// each: dword (round r = 0..3, lane = 0..63), nibble e = 0..7, bit i <-> channel 32 kb + 4 (lane & 7) + i of pixel `pid & 15` (row-major in the
+// 4x4 tile) of the group's tile 4 (pid >> 4) + r (row-major in the group), where pid = 8 e + (lane >> 3).  Both directions of that map:
+constexpr int WINO_MASK_KT = 32;
+__host__ __device__ __forceinline__ long wino_mask_item(const long n, const int gy, const int gx, const int kb, const int GYn, const int GXn, const int KB) { return ((n * GYn + gy) * GXn + gx) * KB + kb; }
+__host__ __device__ __forceinline__ int wino_mask_pid(const int e, const int lane) { return e * 8 + (lane >> 3); }
+__host__ __device__ __forceinline__ int wino_mask_tile(const int pid, const int r) { return 4 * (pid >> 4) + r; }
+__host__ __device__ __forceinline__ int wino_mask_round(const int tile) { return tile & 3; }
+__host__ __device__ __forceinline__ int wino_mask_pid_of(const int tile, const int px) { return 16 * (tile >> 2) + px; }
+__host__ __device__ __forceinline__ int wino_mask_nibble(const int pid) { return pid >> 3; } // e
+__host__ __device__ __forceinline__ int wino_mask_lane(const int pid, const int q8) { return (pid & 7) * 8 + q8; } // q8 = channel quad within the block
+
+// where wino_input_kernel<true> writes the mask bits of the map it transforms (2 x 8 tile groups)
+struct WinoMaskOut {
+	unsigned char* bits;
+	int GYn, GXn, KB; // that kernel's tile groups per image column / row, blocks of 32 channels
+};
+
 // V[z][t][c] = (B^T d B)[zy][zx], d = the 6x6 source patch of tile t (zero outside the image).  One thread per (t, c4):
 // 36 16-byte loads, 12 six-point transforms on float4, 36 16-byte stores (the c4 threads of a tile write contiguous runs).
-static __global__ void __launch_bounds__(256) wino_input_kernel(const float* __restrict__ a, float* __restrict__ v, const WinoTiles g)
+// MASK (source padding 1, so that d[1..4][1..4] is the 4x4 tile t of the source itself): the thread also writes `d > 0` of those 16 pixels x 4 channels
+// as mask bits for a fused data gradient with 2 x 8 tile groups.  Pixels px and px + 8 of a tile are the two nibbles 2 gp, 2 gp + 1 of ONE dword, i.e.
+// its byte gp, so the thread owns eight whole bytes: byte stores, no atomics; pixels outside the image were loaded as zeros and give zero bits.
+template <bool MASK>
+static __global__ void __launch_bounds__(256) wino_input_kernel(const float* __restrict__ a, float* __restrict__ v, const WinoTiles g, const WinoMaskOut mo)
 {
 	const long idx = (long)nnc_xcd_block(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x; // neighbouring tiles share 2 of their 6 rows / columns: same XCD
 	if (idx >= (long)g.T * g.C4) return;
@@ -146,6 +169,7 @@ static __global__ void __launch_bounds__(256) wino_input_kernel(const float* __r
 	const int y0 = ty * 4 + g.oy, x0 = tx * 4 + g.ox;
 	const float* const src = a + (long)n * g.sn + (long)c4 * 4;
 	f4 s[6][6]; // rows transformed horizontally: s[r] = d[r] B
+	unsigned mb[8];
 #pragma unroll
 	for (int r = 0; r < 6; r++) {
 		const int y = y0 + r;
@@ -157,7 +181,26 @@ static __global__ void __launch_bounds__(256) wino_input_kernel(const float* __r
 			const bool ok = yok & (x >= 0) & (x < g.W);
 			d[q] = ok ? f4(*(const float4*)(src + (long)y * g.sh + (long)x * g.sw)) : f4(0.f, 0.f, 0.f, 0.f);
 		}
+		if (MASK && r >= 1 && r <= 4) {
+#pragma unroll
+			for (int q = 0; q < 4; q++) { // pixel px = 4 (r - 1) + q: byte px & 7, nibble px >> 3
+				const f4 m = d[q + 1];
+				const unsigned nib = (m.x > 0.f ? 1u : 0u) | (m.y > 0.f ? 2u : 0u) | (m.z > 0.f ? 4u : 0u) | (m.w > 0.f ? 8u : 0u);
+				const int px = 4 * (r - 1) + q;
+				if (px < 8) mb[px] = nib; else mb[px - 8] |= nib << 4;
+			}
+		}
 		wino_bt(d, s[r]);
+	}
+	if (MASK) {
+		const int gy = ty >> 1, gx = tx >> 3, tile = (ty & 1) * 8 + (tx & 7); // 2 x 8 tile groups
+		const long item = wino_mask_item(n, gy, gx, c4 >> 3, mo.GYn, mo.GXn, mo.KB);
+		unsigned char* const bp = mo.bits + (item * 256 + wino_mask_round(tile) * 64) * 4;
+#pragma unroll
+		for (int j = 0; j < 8; j++) {
+			const int pid = wino_mask_pid_of(tile, j); // ... and of pixel j + 8: the same lane, the next nibble
+			bp[wino_mask_lane(pid, c4 & 7) * 4 + (wino_mask_nibble(pid) >> 1)] = (unsigned char)mb[j];
+		}
 	}
 	const long plane = (long)g.T * g.C4 * 4;
 	float* const dst = v + idx * 4;
@@ -266,6 +309,83 @@ static __global__ void __launch_bounds__(256) wino_outgrad_kernel(const float* _
 			for (int j = threadIdx.x; j < 256; j += g.C4) acc = acc + f4(red[j]);
 			*(float4*)(blockpart + ((long)blockIdx.x * g.C4 + threadIdx.x) * 4) = (float4)acc;
 		}
+	}
+}
+
+// Both transforms of the output gradient in ONE pass over it, for a backward command that computes the data gradient and the filter
+// gradient via HBM (3 x 3, stride 1, padding 1: the data gradient's 6x6 patch of tile t starts at (4 ty - 1, 4 tx - 1), and the filter
+// gradient's 4x4 tile t is the middle of that patch -- g.oy = g.ox = -1, g.H / g.W = the gradient's extent, which is also the extent
+// both tile grids cover).  One thread per (t, k4):
+//   v [z][t][k] = (B^T d B)[zy][zx]                    wino_input_kernel's expressions on the patch d
+//   wt[z][t][k] = (G' d[1..4][1..4] G'^T)[zy][zx]      wino_outgrad_kernel's on its middle
+//   blockpart[block][K]                                 that kernel's column sums: same 16 pixels in the same order per thread, same fold
+//                                                       per block of 256 consecutive (t, k4), same row per block
+// so each of the three is bit for bit what wino_input_kernel and wino_outgrad_kernel<true> write, and colsum_f32 over blockpart is unchanged.  The
+// block that covers threads [256 b, 256 b + 256) is found through nnc_xcd_block as in wino_input_kernel (neighbouring patches overlap).
+// There is no form without the column sums: hipcc contracts a * b + c * d into an fma across statements, and WHICH product goes inside depends on
+// what else uses the operands -- next to the column sums the compiler makes the choices it makes in wino_outgrad_kernel<true> (tests/
+// test_wino_backward_once.py holds it to that on the MI355X), without them W came out a last bit away from wino_outgrad_kernel<false>'s, and
+// pinning the operands (asm barriers) costs 300 moves and half the occupancy.  Commands without a fused bias gradient keep the two kernels.
+static __global__ void __launch_bounds__(256) wino_outgrad_both_kernel(const float* __restrict__ gr, float* __restrict__ v, float* __restrict__ wt, const WinoTiles g, float* __restrict__ blockpart)
+{
+	__shared__ float4 red[256];
+	const unsigned block = nnc_xcd_block(blockIdx.x, gridDim.x);
+	const long idx = (long)block * blockDim.x + threadIdx.x;
+	const bool live = idx < (long)g.T * g.C4;
+	f4 sum(0.f, 0.f, 0.f, 0.f);
+	if (live) {
+		const int t = g.d_c4.div((int)idx), k4 = (int)(idx - (long)t * g.C4);
+		const int tn = g.d_tw.div(t), tx = t - tn * g.TW;
+		const int n = g.d_th.div(tn), ty = tn - n * g.TH;
+		const int y0 = ty * 4 + g.oy, x0 = tx * 4 + g.ox;
+		const float* const src = gr + (long)n * g.sn + (long)k4 * 4;
+		const long plane = (long)g.T * g.C4 * 4;
+		f4 s[6][6];  // patch rows transformed horizontally: s[r] = d[r] B
+		f4 sg[4][6]; // middle rows: sg[r - 1] = d[r][1..4] G'^T
+#pragma unroll
+		for (int r = 0; r < 6; r++) {
+			const int y = y0 + r;
+			const bool yok = (y >= 0) & (y < g.H);
+			f4 d[6];
+#pragma unroll
+			for (int q = 0; q < 6; q++) {
+				const int x = x0 + q;
+				const bool ok = yok & (x >= 0) & (x < g.W);
+				d[q] = ok ? f4(*(const float4*)(src + (long)y * g.sh + (long)x * g.sw)) : f4(0.f, 0.f, 0.f, 0.f);
+			}
+			wino_bt(d, s[r]);
+			if (r >= 1 && r <= 4) {
+				const f4 m[4] = { d[1], d[2], d[3], d[4] };
+#pragma unroll
+				for (int q = 0; q < 4; q++) sum = sum + m[q];
+				wino_g4(m, sg[r - 1]);
+			}
+		}
+		float* const dst = v + idx * 4;
+#pragma unroll
+		for (int q = 0; q < 6; q++) {
+			const f4 col[6] = { s[0][q], s[1][q], s[2][q], s[3][q], s[4][q], s[5][q] };
+			f4 y[6];
+			wino_bt(col, y);
+#pragma unroll
+			for (int r = 0; r < 6; r++) *(float4*)(dst + (long)(r * 6 + q) * plane) = y[r];
+		}
+		float* const dstw = wt + idx * 4;
+#pragma unroll
+		for (int q = 0; q < 6; q++) {
+			const f4 col[4] = { sg[0][q], sg[1][q], sg[2][q], sg[3][q] };
+			f4 y[6];
+			wino_g4(col, y);
+#pragma unroll
+			for (int r = 0; r < 6; r++) *(float4*)(dstw + (long)(r * 6 + q) * plane) = y[r];
+		}
+	}
+	red[threadIdx.x] = (float4)sum;
+	__syncthreads();
+	if ((int)threadIdx.x < g.C4) { // as in wino_outgrad_kernel: thread k4 owns channel group k4
+		f4 acc(0.f, 0.f, 0.f, 0.f);
+		for (int j = threadIdx.x; j < 256; j += g.C4) acc = acc + f4(red[j]);
+		*(float4*)(blockpart + ((long)block * g.C4 + threadIdx.x) * 4) = (float4)acc;
 	}
 }
 

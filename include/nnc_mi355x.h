@@ -378,6 +378,13 @@ int  nnc_mi355x_profile_get(int i, char* name, int name_len, double* flops, doub
  * tile shape on every loader at sizes the oracle finishes. */
 void nnc_mi355x_debug_force_tile(int wm, int wn);
 void nnc_mi355x_debug_force_splits(int splits);
+/* Test hook: the next CONVOLUTION_BACKWARD whose data gradient is the fused Winograd kernel under NNC_MI355X_CONV_ALGO_FUSE_RELU copies that kernel's
+ * mask bits (1 KB per tile group and 32-channel block, wino_fused.h) to `dst` (host memory, at most `capacity` bytes) and waits for the copy; one shot.
+ * Returns the size in bytes of the buffer the last such copy was taken from (0: none yet); dst = 0 only asks for that. */
+size_t nnc_mi355x_debug_conv_mask_bits(void* dst, size_t capacity);
+/* Test hook: how many backward convolutions of this process read a tensor once for both gradients (tunable CONV_BACK_SHARE): what = 0 the output gradient
+ * transformed for the data gradient and the filter gradient by one kernel, what = 1 the mask bits written by the filter gradient's input transform. */
+long nnc_mi355x_debug_conv_back_shared(int what);
 /* Bytes of reserved space LSTM_FORWARD writes (output 3) and LSTM_BACKWARD reads (input 12) -- the function both LSTM rows carry in registry->aux,
  * which the host's shape inference calls through ccv_nnc_cmd_aux (lib/nnc/cmd/rnn/ccv_nnc_lstm.c:35,64-71); replaces
  * _ccv_nnc_lstm_reserve_space_size / cudnnGetRNNTempSpaceSizes (lib/nnc/cmd/rnn/gpu/ccv_nnc_lstm_gpu_cudnn.cu:17-48).  0 when cmd.info.rnn.is_test. */
