@@ -11,6 +11,7 @@
 #include "wino_fused.h"
 #include "wino_wgrad_fused.h"
 #include "conv_c3.h"
+#include "conv_depthwise.h"
 
 using namespace nnc;
 
@@ -939,6 +940,238 @@ static void dense_nhwc_like(const ccv_nnc_tensor_t* like, const Image4& li, floa
 	out->data.f32 = data;
 }
 
+// ---- depthwise convolutions (conv_depthwise.h) ------------------------------------------------------------------------------------
+// groups == channels == filters, at least 8 of them: a kh x kw stencil per channel, bound by HBM -- as `groups` implicit GEMMs with ONE output column each
+// (and, in NCHW, between layout passes) it used almost none of the machine.  Taken (TUNE_CONV_DEPTHWISE) when every tensor is dense, of the one element
+// type T and -- activations -- of one format, on 16-byte aligned bases, with C a whole number of 16-byte vectors where channels are innermost; everything
+// else (views, mixed precision, channel multipliers, odd channel counts in NHWC) keeps the route it had.  CCV_NNC_EXEC_NO_KERNEL = not this path.
+static thread_local int tl_dw_staged = 0; // the command in progress runs on fp32 images of its tensors (half_staged_exec)
+template <class T> struct conv_dw_type;
+template <> struct conv_dw_type<float> { enum { datatype = CCV_32F }; };
+template <> struct conv_dw_type<half_t> { enum { datatype = CCV_16F }; };
+
+template <class T>
+static bool conv_dw_dense(const ccv_nnc_tensor_t* t)
+{
+	return CCV_GET_DATA_TYPE(t->info.datatype) == (int)conv_dw_type<T>::datatype && tensor_contiguous(t);
+}
+
+// in / out: the forward input's and output's shapes (tensors of the command that have them); *nhwc: the activations' format
+template <class T>
+static bool conv_dw_eligible(const ccv_nnc_cmd_t& cmd, const ccv_nnc_hint_t& hint, const ccv_nnc_tensor_t* in, const ccv_nnc_tensor_t* out, const ccv_nnc_tensor_t* wshape, conv_geom_t* g, bool* nhwc)
+{
+	if (!tune(TUNE_CONV_DEPTHWISE) || tl_dw_staged || cmd.algorithm == CONV_ALGO_IMPLICIT_GEMM || !in || !out || !wshape) return false;
+	if (in->info.format != out->info.format || (in->info.format != CCV_TENSOR_FORMAT_NHWC && in->info.format != CCV_TENSOR_FORMAT_NCHW)) return false;
+	Image4 ii, oi;
+	if (!image4(in, &ii) || !image4(out, &oi) || !conv_geometry(cmd, hint, ii, oi, 0, g)) return false;
+	if (g->groups != g->C || g->C != g->K || g->C < 8) return false;
+	int K, kh, kw, Cg;
+	if (!weights_shape(wshape, &K, &kh, &kw, &Cg) || K != g->K || kh != g->kh || kw != g->kw || Cg != 1) return false;
+	if (kh < 1 || kw < 1 || kh > DW_MAX_K || kw > DW_MAX_K || g->sy > 4 || g->sx > 4 || g->N < 1 || g->H < 1 || g->W < 1 || g->OH < 1 || g->OW < 1) return false;
+	*nhwc = in->info.format == CCV_TENSOR_FORMAT_NHWC;
+	if (*nhwc && g->C % (int)DwVec<T>::V) return false;
+	// 32-bit pixel / plane / row counts in the kernels
+	if ((long)g->N * g->H * g->W > 0x7fffffffL || (long)g->N * g->OH * g->OW > 0x7fffffffL || (long)g->N * g->C > 0x3fffffffL) return false;
+	return true;
+}
+template <class T>
+static bool conv_dw_tensor_ok(const ccv_nnc_tensor_t* t) { return !t || (conv_dw_dense<T>(t) && aligned16(t->data.u8)); }
+
+static void conv_dw_geom(const conv_geom_t& g, DwGeom* d)
+{ // the forward orientation: reads the input, writes the output
+	d->N = g.N; d->C = g.C; d->SH = g.H; d->SW = g.W; d->DH = g.OH; d->DW = g.OW;
+	d->kh = g.kh; d->kw = g.kw; d->sy = g.sy; d->sx = g.sx; d->py = g.pby; d->px = g.pbx; d->dy = g.dy; d->dx = g.dx;
+	d->holes = 0; d->flip = 0;
+}
+static void conv_dw_geom_dgrad(const conv_geom_t& g, DwGeom* d)
+{ // reads the output gradient, writes the input gradient: stride 1 = the forward stencil mirrored, else the hole pattern
+	conv_dw_geom(g, d);
+	d->SH = g.OH; d->SW = g.OW; d->DH = g.H; d->DW = g.W;
+	if (g.sy == 1 && g.sx == 1) { d->flip = 1; d->py = (g.kh - 1) * g.dy - g.pby; d->px = (g.kw - 1) * g.dx - g.pbx; }
+	else d->holes = 1;
+}
+
+// NCHW stencil: planes per workgroup, or -- a plane larger than DW_LDS_SRC -- output rows per band so that the source rows a band reads fit
+static bool conv_dw_nchw_plan(const DwGeom& d, int* P, int* TB, int* nbands)
+{
+	const long plane = (long)d.SH * d.SW;
+	if (plane <= DW_LDS_SRC) {
+		const long p = DW_LDS_SRC / plane;
+		*P = p < DW_MAX_PLANES ? (int)p : DW_MAX_PLANES; *TB = d.DH; *nbands = 1;
+		return true;
+	}
+	const int rows = DW_LDS_SRC / d.SW, reach = (d.kh - 1) * d.dy;
+	long tb;
+	if (!d.holes) tb = rows > reach ? (rows - reach - 1) / d.sy + 1 : 0; // a band reads (tb - 1) * sy + reach + 1 rows
+	else tb = (long)(rows - 2) * d.sy - reach + 1;                       // ... at most (tb - 1 + reach) / sy + 2
+	if (tb < 1) return false;
+	if (tb > d.DH) tb = d.DH;
+	*nbands = (int)((d.DH + tb - 1) / tb); *TB = (d.DH + *nbands - 1) / *nbands; *P = 1;
+	return true;
+}
+
+template <class T>
+static int conv_dw_stencil(const char* name, const bool nhwc, const DwGeom& d, const T* src, const T* w, const T* bias, T* dst, ccv_nnc_stream_context_t* const ctx)
+{
+	constexpr int V = DwVec<T>::V;
+	const int kk = d.kh * d.kw;
+	const double flops = 2.0 * d.N * d.DH * d.DW * (double)d.C * kk, bytes = sizeof(T) * ((double)d.N * d.C * ((double)d.SH * d.SW + (double)d.DH * d.DW) + (double)d.C * kk);
+	char prof_name[96];
+	if (nhwc) {
+		const int CV = d.C / V, cvb = CV < DW_CHAN_BLOCK / V ? CV : DW_CHAN_BLOCK / V, ncb = (CV + cvb - 1) / cvb, PB = 256 / cvb;
+		const int pixels = d.N * d.DH * d.DW;
+		long pixblocks = ((long)pixels + PB - 1) / PB;
+		const long cap = (long)device_cu_count() * 16 / ncb > 0 ? (long)device_cu_count() * 16 / ncb : 1; // each workgroup stages its channel block's filter once
+		if (pixblocks > cap) pixblocks = cap;
+		FastDiv d_w, d_h;
+		d_w.init(d.DW); d_h.init(d.DH);
+		hipStream_t stream = stream_of(ctx);
+		note_kernel(name);
+		snprintf(prof_name, sizeof(prof_name), "%s|nnc::conv_dw_nhwc_kernel", name);
+		ProfScope prof(prof_name, flops, bytes, pixels, d.C, kk, 1, 1, stream);
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_dw_nhwc_kernel<T>), dim3((unsigned)(pixblocks * ncb)), dim3(256), sizeof(float) * kk * cvb * V, stream, src, w, bias, dst, d, CV, cvb, ncb, (int)pixblocks, pixels, d_w, d_h);
+		HIP_ENFORCE(hipGetLastError());
+		return CCV_NNC_EXEC_SUCCESS;
+	}
+	int P, TB, nbands;
+	if (!conv_dw_nchw_plan(d, &P, &TB, &nbands)) return CCV_NNC_EXEC_NO_KERNEL;
+	const int planes = d.N * d.C;
+	const long grid = (long)((planes + P - 1) / P) * nbands;
+	if (grid > 0x7fffffffL) return CCV_NNC_EXEC_NO_KERNEL;
+	const int K = d.kh == d.kw && (d.kh == 3 || d.kh == 5) && d.sy == d.sx && d.sy <= 2 && d.dy == 1 && d.dx == 1 && !d.holes ? d.kh : 0; // the register-segment form
+	FastDiv d_x, d_t;
+	d_x.init(K ? (d.DW + DW_RUN - 1) / DW_RUN : d.DW); d_t.init(TB);
+	hipStream_t stream = stream_of(ctx);
+	note_kernel(name);
+	snprintf(prof_name, sizeof(prof_name), "%s|nnc::conv_dw_nchw_kernel<%d, %d>", name, K, K ? d.sy : 0);
+	ProfScope prof(prof_name, flops, bytes, d.N * d.DH * d.DW, d.C, kk, 1, 1, stream);
+#define NNC_DW_NCHW(KK, SS) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_dw_nchw_kernel<T, KK, SS>), dim3((unsigned)grid), dim3(256), sizeof(float) * P * kk, stream, src, w, bias, dst, d, planes, P, TB, nbands, d_x, d_t)
+	if (K == 3 && d.sy == 1) NNC_DW_NCHW(3, 1);
+	else if (K == 3) NNC_DW_NCHW(3, 2);
+	else if (K == 5 && d.sy == 1) NNC_DW_NCHW(5, 1);
+	else if (K == 5) NNC_DW_NCHW(5, 2);
+	else NNC_DW_NCHW(0, 1);
+#undef NNC_DW_NCHW
+	HIP_ENFORCE(hipGetLastError());
+	return CCV_NNC_EXEC_SUCCESS;
+}
+
+// NCHW filter gradient: whole planes of a and g -- PC channels (at most 8) of NB images -- where PC * NB of the larger plane fit DW_LDS_WGRAD, else bands of
+// TB output-gradient rows of one plane whose input rows fit.  Slices = ceil(N / NB) * bands.
+static bool conv_dw_wgrad_nchw_plan(const DwGeom& d, int* PC, int* NB, int* TB, int* nbands)
+{
+	const long xplane = (long)d.SH * d.SW, gplane = (long)d.DH * d.DW, big = xplane > gplane ? xplane : gplane;
+	if (big <= DW_LDS_WGRAD) {
+		const int np = (int)(DW_LDS_WGRAD / big);
+		int pc = d.C < 8 ? d.C : 8;
+		if (pc > np) pc = np;
+		int nb = np / pc;
+		if (nb > d.N) nb = d.N;
+		*PC = pc; *NB = nb; *TB = d.DH; *nbands = 1;
+		return true;
+	}
+	const int rows = DW_LDS_WGRAD / d.SW, need = (d.kh - 1) * d.dy + 1;
+	if (rows < need || d.DW > DW_LDS_WGRAD) return false;
+	int tb = (rows - need) / d.sy + 1;
+	if (tb > DW_LDS_WGRAD / d.DW) tb = DW_LDS_WGRAD / d.DW;
+	if (tb > d.DH) tb = d.DH;
+	*PC = 1; *NB = 1; *nbands = (d.DH + tb - 1) / tb; *TB = (d.DH + *nbands - 1) / *nbands;
+	return true;
+}
+
+// dw (+)= , dbias (+)= (either may be absent) in one pass over g and a, partials in the stream workspace, then the fold.
+// NHWC slices: the N * OH output rows in row slices of max(4, ceil(N * OH / 1024)) rows, times the Q = 256 / (channel vectors of the block * (kh * kw + 1))
+// pixel phases of a workgroup.
+template <class T>
+static int conv_dw_wgrad(const bool nhwc, const DwGeom& d, const T* gr, const T* a, T* dw, T* dbias, const int accumulate, ccv_nnc_stream_context_t* const ctx)
+{
+	constexpr int V = DwVec<T>::V;
+	const int kk = d.kh * d.kw;
+	const double flops = 2.0 * d.N * d.DH * d.DW * (double)d.C * (kk + 1), bytes = sizeof(T) * ((double)d.N * d.C * ((double)d.SH * d.SW + (double)d.DH * d.DW) + (double)d.C * (kk + 1));
+	long slices;
+	float* partial;
+	hipStream_t stream;
+	if (nhwc) {
+		const int CV = d.C / V, cvb = CV < 256 / (kk + 1) ? CV : 256 / (kk + 1), ncb = (CV + cvb - 1) / cvb, Q = 256 / (cvb * (kk + 1));
+		const int rows = d.N * d.DH;
+		int rows_per = (rows + 1023) / 1024;
+		if (rows_per < 4) rows_per = 4;
+		const int nrs = (rows + rows_per - 1) / rows_per;
+		slices = (long)nrs * Q;
+		partial = (float*)workspace_of(ctx, sizeof(float) * (size_t)slices * d.C * (kk + 1));
+		if (!partial) return CCV_NNC_EXEC_OOM;
+		FastDiv d_oh;
+		d_oh.init(d.DH);
+		stream = stream_of(ctx);
+		note_kernel("conv_dw_wgrad");
+		ProfScope prof("conv_dw_wgrad|nnc::conv_dw_wgrad_nhwc_kernel", flops, bytes, d.C, kk + 1, rows * d.DW, 1, (int)slices, stream);
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_dw_wgrad_nhwc_kernel<T>), dim3((unsigned)(nrs * ncb)), dim3(256), 0, stream, gr, a, partial, d, CV, cvb, ncb, Q, rows_per, rows, d_oh);
+		HIP_ENFORCE(hipGetLastError());
+	} else {
+		int PC, NB, TB, nbands;
+		if (!conv_dw_wgrad_nchw_plan(d, &PC, &NB, &TB, &nbands)) return CCV_NNC_EXEC_NO_KERNEL;
+		const int ncb = (d.C + PC - 1) / PC, NG = (d.N + NB - 1) / NB;
+		int Q = 1;
+		while (Q < 64 && Q < d.DW) Q <<= 1;
+		const long grid = (long)NG * ncb * nbands;
+		if (grid > 0x7fffffffL) return CCV_NNC_EXEC_NO_KERNEL;
+		slices = (long)NG * nbands;
+		partial = (float*)workspace_of(ctx, sizeof(float) * (size_t)slices * d.C * (kk + 1));
+		if (!partial) return CCV_NNC_EXEC_OOM;
+		stream = stream_of(ctx);
+		note_kernel("conv_dw_wgrad");
+		ProfScope prof("conv_dw_wgrad|nnc::conv_dw_wgrad_nchw_kernel", flops, bytes, d.C, kk + 1, d.N * d.DH * d.DW, 1, (int)slices, stream);
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_dw_wgrad_nchw_kernel<T>), dim3((unsigned)grid), dim3(256), 0, stream, gr, a, partial, d, PC, NB, TB, nbands, ncb, Q);
+		HIP_ENFORCE(hipGetLastError());
+	}
+	note_kernel("conv_dw_fold");
+	ProfScope prof("conv_dw_fold|nnc::conv_dw_fold_kernel", (double)slices * d.C * (kk + 1), sizeof(float) * (double)slices * d.C * (kk + 1), d.C, kk + 1, (int)slices, 1, 1, stream);
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_dw_fold_kernel<T>), dim3((unsigned)((d.C * (kk + 1) + FOLD_CH - 1) / FOLD_CH)), dim3(256), 0, stream, (const float*)partial, slices, d.C, kk, dw, dbias, accumulate);
+	HIP_ENFORCE(hipGetLastError());
+	return CCV_NNC_EXEC_SUCCESS;
+}
+
+template <class T>
+static int conv_dw_forw(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* w, const ccv_nnc_tensor_t* bias, ccv_nnc_tensor_t* b, ccv_nnc_stream_context_t* const ctx)
+{
+	conv_geom_t g;
+	bool nhwc;
+	if ((flags & CCV_NNC_ACCUMULATE_OUTPUT) || !conv_dw_eligible<T>(cmd, hint, a, b, w, &g, &nhwc)) return CCV_NNC_EXEC_NO_KERNEL;
+	if (!conv_dw_tensor_ok<T>(a) || !conv_dw_tensor_ok<T>(b) || !conv_dw_dense<T>(w) || (bias && (!conv_dw_dense<T>(bias) || (int)tensor_count(bias->info) != g.C))) return CCV_NNC_EXEC_NO_KERNEL;
+	DwGeom d;
+	conv_dw_geom(g, &d);
+	// (NNC_MI355X_CONV_ALGO_FUSE_RELU: tl_relu_done stays 0 -- the in-place pass of conv_forw_entry follows, the bits are the unfused pair's by construction)
+	return conv_dw_stencil<T>("conv_dw_fwd", nhwc, d, (const T*)a->data.u8, (const T*)w->data.u8, bias ? (const T*)bias->data.u8 : 0, (T*)b->data.u8, ctx);
+}
+
+template <class T>
+static int conv_dw_back(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, const ccv_nnc_tensor_t* gt, const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* w, ccv_nnc_tensor_t* h, ccv_nnc_tensor_t* dw, ccv_nnc_tensor_t* dbias, ccv_nnc_stream_context_t* const ctx)
+{
+	const ccv_nnc_tensor_t* const shape_src = a ? a : h;
+	const ccv_nnc_tensor_t* const wshape = dw ? dw : w;
+	conv_geom_t g;
+	bool nhwc;
+	if (!conv_dw_eligible<T>(cmd, hint, shape_src, gt, wshape, &g, &nhwc)) return CCV_NNC_EXEC_NO_KERNEL;
+	if (!conv_dw_tensor_ok<T>(gt) || !conv_dw_tensor_ok<T>(a) || !conv_dw_tensor_ok<T>(h) || (w && !conv_dw_dense<T>(w)) || (dw && !conv_dw_dense<T>(dw)) || (dbias && (!conv_dw_dense<T>(dbias) || (int)tensor_count(dbias->info) != g.C))) return CCV_NNC_EXEC_NO_KERNEL;
+	if ((dw && !a) || (h && !w) || (a && a->info.format != gt->info.format) || (h && h->info.format != gt->info.format)) return CCV_NNC_EXEC_NO_KERNEL;
+	if (w && dw && w->info.format != dw->info.format) return CCV_NNC_EXEC_NO_KERNEL;
+	if (w && (long)tensor_count(w->info) != (long)g.C * g.kh * g.kw) return CCV_NNC_EXEC_NO_KERNEL;
+	Image4 hi;
+	if (h && (!image4(h, &hi) || hi.n != g.N || hi.h != g.H || hi.w != g.W || hi.c != g.C)) return CCV_NNC_EXEC_NO_KERNEL;
+	DwGeom d, dd;
+	conv_dw_geom(g, &d);
+	conv_dw_geom_dgrad(g, &dd);
+	// every kernel below must apply before anything is launched: the other route takes the WHOLE command
+	int P, TB, nbands, PC, NB;
+	if (!nhwc && ((h && !conv_dw_nchw_plan(dd, &P, &TB, &nbands)) || ((dw || dbias) && a && !conv_dw_wgrad_nchw_plan(d, &PC, &NB, &TB, &nbands)))) return CCV_NNC_EXEC_NO_KERNEL;
+	if (dbias && !a) return CCV_NNC_EXEC_NO_KERNEL; // (a bias gradient alone, without the forward input: the column sums of the other route)
+	int ret;
+	if ((dw || dbias) && (ret = conv_dw_wgrad<T>(nhwc, d, (const T*)gt->data.u8, (const T*)a->data.u8, dw ? (T*)dw->data.u8 : 0, dbias ? (T*)dbias->data.u8 : 0, (flags & CCV_NNC_ACCUMULATE_OUTPUT) ? 1 : 0, ctx)) != CCV_NNC_EXEC_SUCCESS) return ret;
+	// (a masked data gradient -- tl_mask_want -- is left to conv_back_entry's relu_back_inplace)
+	if (h && (ret = conv_dw_stencil<T>("conv_dw_dgrad", nhwc, dd, (const T*)gt->data.u8, (const T*)w->data.u8, (const T*)0, (T*)h->data.u8, ctx)) != CCV_NNC_EXEC_SUCCESS) return ret;
+	return CCV_NNC_EXEC_SUCCESS;
+}
+
 static int _conv_forw(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
 {
 	if (input_size < 2 || output_size < 1 || !inputs[0] || !inputs[1] || !outputs[0]) return CCV_NNC_EXEC_INVALID;
@@ -948,6 +1181,10 @@ static int _conv_forw(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const 
 	ccv_nnc_tensor_t* b = outputs[0];
 	if (CCV_GET_DATA_TYPE(a->info.datatype) != CCV_32F) return CCV_NNC_EXEC_INVALID;
 	if (a->info.format != b->info.format) return CCV_NNC_EXEC_INVALID;
+	{
+		const int r = conv_dw_forw<float>(cmd, hint, flags, a, w, bias, b, stream_context);
+		if (r != CCV_NNC_EXEC_NO_KERNEL) return r;
+	}
 	if (a->info.format == CCV_TENSOR_FORMAT_NCHW && cmd.algorithm != CONV_ALGO_IMPLICIT_GEMM) {
 		const int r = conv1x1_nchw_forw<float>(cmd, hint, flags, a, w, bias, b, stream_context);
 		if (r != CCV_NNC_EXEC_NO_KERNEL) return r;
@@ -998,6 +1235,10 @@ static int _conv_back(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const 
 	ccv_nnc_tensor_t* dw = output_size > 1 ? outputs[1] : 0;
 	ccv_nnc_tensor_t* dbias = output_size > 2 ? outputs[2] : 0;
 	if (CCV_GET_DATA_TYPE(gt->info.datatype) != CCV_32F) return CCV_NNC_EXEC_INVALID;
+	{
+		const int r = conv_dw_back<float>(cmd, hint, flags, gt, a, w, h, dw, dbias, stream_context);
+		if (r != CCV_NNC_EXEC_NO_KERNEL) return r;
+	}
 	if (gt->info.format == CCV_TENSOR_FORMAT_NCHW && cmd.algorithm != CONV_ALGO_IMPLICIT_GEMM) {
 		const int r = conv1x1_nchw_back<float>(cmd, hint, flags, gt, a, w, h, dw, dbias, stream_context);
 		if (r != CCV_NNC_EXEC_NO_KERNEL) return r;
@@ -1434,6 +1675,10 @@ static int _conv_forw_half(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, c
 	const ccv_nnc_tensor_t* w = inputs[1];
 	const ccv_nnc_tensor_t* bias = input_size > 2 ? inputs[2] : 0;
 	ccv_nnc_tensor_t* b = outputs[0];
+	{
+		const int r = conv_dw_forw<half_t>(cmd, hint, flags, a, w, bias, b, stream_context);
+		if (r != CCV_NNC_EXEC_NO_KERNEL) return r;
+	}
 	if (a->info.format == CCV_TENSOR_FORMAT_NCHW && b->info.format == CCV_TENSOR_FORMAT_NCHW) {
 		const int r = conv1x1_nchw_forw<half_t>(cmd, hint, flags, a, w, bias, b, stream_context);
 		return r != CCV_NNC_EXEC_NO_KERNEL ? r : conv_nchw_half_forw(cmd, hint, flags, a, w, bias, b, stream_context);
@@ -1462,6 +1707,10 @@ static int _conv_back_half(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, c
 	const ccv_nnc_tensor_t* shape_src = a ? a : h;
 	const ccv_nnc_tensor_t* wshape = dw ? dw : w;
 	if (!shape_src || !wshape) return CCV_NNC_EXEC_INVALID;
+	{
+		const int r = conv_dw_back<half_t>(cmd, hint, flags, gt, a, w, h, dw, dbias, stream_context);
+		if (r != CCV_NNC_EXEC_NO_KERNEL) return r;
+	}
 	if (gt->info.format == CCV_TENSOR_FORMAT_NCHW) {
 		const int r = conv1x1_nchw_back<half_t>(cmd, hint, flags, gt, a, w, h, dw, dbias, stream_context);
 		return r != CCV_NNC_EXEC_NO_KERNEL ? r : conv_nchw_half_back(cmd, hint, flags, gt, a, w, h, dw, dbias, stream_context);
@@ -1505,7 +1754,10 @@ static int conv_forw_dispatch(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint
 		const int r = _conv_forw_half(cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
 		if (r != CCV_NNC_EXEC_NO_KERNEL) return r;
 	}
-	return half_staged_exec(_conv_forw, cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
+	tl_dw_staged = 1; // (fp32 images of half or mixed tensors: the route such a command had, not the depthwise kernels on the images)
+	const int r = half_staged_exec(_conv_forw, cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
+	tl_dw_staged = 0;
+	return r;
 }
 static int conv_forw_entry(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context);
 // The registered entry: a convolution whose like has run before is recorded, not launched -- the in-place RELU_FORWARD the reference's
@@ -1583,7 +1835,10 @@ static int conv_back_dispatch(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint
 		const int r = _conv_back_half(cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
 		if (r != CCV_NNC_EXEC_NO_KERNEL) return r;
 	}
-	return half_staged_exec(_conv_back, cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
+	tl_dw_staged = 1;
+	const int r = half_staged_exec(_conv_back, cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
+	tl_dw_staged = 0;
+	return r;
 }
 
 // autotune (ccv_nnc.h:323; what lib/nnc/cmd/convolution/gpu/ccv_nnc_conv_gpu_cudnn.cu:116-202 does with cudnnFind*): run the

@@ -255,6 +255,7 @@ enum {
 	TUNE_BN_CLUSTER_SLOTS,  // the cluster batch-norm kernels on tensors too small to fill the chip with full workgroup shares: shares are cut down until the launch has about this many workgroups (never below two chunks per thread); 0 = always the largest share a workgroup's registers hold (rounds 4 - 5)
 	TUNE_GEMM_BATCH_XCD,    // batched contractions without split-K (a 1 x 1 convolution on NCHW tensors: one matrix product per image) launch ONE grid dimension over (entry, tile) and give every batch entry to one XCD: the tiles of an entry meet in ONE L2, so its B operand -- the image's planes, which every row block of the output reads -- leaves HBM once, not once per XCD (1); 0 = entries on grid z, tiles dealt round-robin over the XCDs (rounds 1 - 5)
 	TUNE_CONV_BACK_SHARE,   // a backward convolution that computes both gradients reads a tensor ONCE where two of its kernels read the same one: bit 0 = the output gradient's two Winograd transforms (data gradient V, filter gradient W, bias sums) in one kernel, bit 1 = the fused data gradient's ReLU mask bits written by the filter gradient's input transform; 0 = the separate kernels (rounds 1 - 6; the results are bit for bit the same)
+	TUNE_CONV_DEPTHWISE,    // depthwise convolutions (groups == channels == filters, dense tensors of one type and one format) on the direct stencil kernels of conv_depthwise.h (1), or as `groups` one-column implicit GEMMs (0)
 	TUNE_COUNT
 };
 static_assert(TUNE_GRID_WG_PER_CU == 3, "grid_for() above names this key by value");
