@@ -71,6 +71,8 @@ CMD = dict(
     SIGMOID_BINARY_CROSSENTROPY_BACKWARD=0xd9e0e4b, SMOOTH_L1_FORWARD=0x4e428e, SMOOTH_L1_BACKWARD=0x4e428f,
     SOFTMAX_FORWARD=0xc969a252, SOFTMAX_BACKWARD=0xc969a253, SWISH_FORWARD=0x583d90c2, SWISH_BACKWARD=0x583d90c3,
     TANH_FORWARD=0x6a62be30, TANH_BACKWARD=0x6a62be31, UPSAMPLE_FORWARD=0x73875556, UPSAMPLE_BACKWARD=0x73875557,
+    MASKED_FILL_FORWARD=0x7f992d84, MASKED_FILL_BACKWARD=0x7f992d85, REDUCE_ISNAN_FORWARD=0xee0a4ade, REDUCE_ISNAN_BACKWARD=0xee0a4adf,
+    DATATYPE_CONVERSION_BACKWARD=0xd873e38d,
 )
 
 _DT_NP = {CCV_32F: np.float32, CCV_32S: np.int32, CCV_64F: np.float64, CCV_16F: np.float16, CCV_8U: np.uint8, CCV_64S: np.int64}
@@ -131,6 +133,10 @@ class _Clamp(C.Structure):
     _fields_ = [("min", C.c_float), ("max", C.c_float)]
 
 
+class _Nms(C.Structure):  # ccv_nnc.h:249-251
+    _fields_ = [("iou_threshold", C.c_float)]
+
+
 class _Gelu(C.Structure):
     _fields_ = [("tanh", C.c_int)]
 
@@ -181,7 +187,7 @@ class _Dropout(C.Structure):  # ccv_nnc.h:235-238
 
 class _CmdUnion(C.Union):
     _fields_ = [("convolution", _Conv), ("convolution_transpose", _ConvTranspose), ("bnorm", _Bnorm), ("sgd", _Sgd), ("blas", _Blas), ("label_smoothing", _LabelSmoothing),
-                ("reduce", _Reduce), ("transpose", _Transpose), ("clamp", _Clamp), ("gelu", _Gelu), ("leaky_relu", _LeakyRelu),
+                ("reduce", _Reduce), ("transpose", _Transpose), ("clamp", _Clamp), ("nms", _Nms), ("gelu", _Gelu), ("leaky_relu", _LeakyRelu),
                 ("adam", _Adam), ("rmsprop", _Rmsprop), ("f1", _F1), ("i1", _I1), ("pad", _Pad), ("upsample", _Upsample), ("lnorm", _Lnorm), ("gnorm", _Gnorm), ("rnn", _Rnn), ("dropout", _Dropout), ("_widest", C.c_char * 68), ("userdata", C.c_void_p)]
 
 
@@ -355,6 +361,69 @@ def CMD_REDUCE_SUM_FORWARD(*axis): return _reduce("REDUCE_SUM_FORWARD", *axis)
 def CMD_REDUCE_SUM_BACKWARD(*axis): return _reduce("REDUCE_SUM_BACKWARD", *axis)
 def CMD_REDUCE_MEAN_FORWARD(*axis): return _reduce("REDUCE_MEAN_FORWARD", *axis)
 def CMD_REDUCE_MEAN_BACKWARD(*axis): return _reduce("REDUCE_MEAN_BACKWARD", *axis)
+
+
+def CMD_REDUCE_ISNAN_FORWARD(*axis): return _reduce("REDUCE_ISNAN_FORWARD", *axis)
+def CMD_REDUCE_NORM2_FORWARD(*axis): return _reduce("REDUCE_NORM2_FORWARD", *axis)
+def CMD_REDUCE_NORM2_BACKWARD(*axis): return _reduce("REDUCE_NORM2_BACKWARD", *axis)
+
+
+# element-wise rows without parameters (ccv_nnc_cmd_easy.h: ccv_nnc_cmd_auto, CMUL with size {1, 1, 1})
+def CMD_EWDIV_FORWARD(): return _cmd("EWDIV_FORWARD", (0, 0, 0))
+def CMD_EWDIV_BACKWARD(): return _cmd("EWDIV_BACKWARD", (0, 0, 0))
+def CMD_EWEXP_FORWARD(): return _cmd("EWEXP_FORWARD", (0, 0, 0))
+def CMD_EWEXP_BACKWARD(): return _cmd("EWEXP_BACKWARD", (0, 0, 0))
+def CMD_EWLOG_FORWARD(): return _cmd("EWLOG_FORWARD", (0, 0, 0))
+def CMD_EWLOG_BACKWARD(): return _cmd("EWLOG_BACKWARD", (0, 0, 0))
+def CMD_EWSQRT_FORWARD(): return _cmd("EWSQRT_FORWARD", (0, 0, 0))
+def CMD_EWSQRT_BACKWARD(): return _cmd("EWSQRT_BACKWARD", (0, 0, 0))
+def CMD_MIN_FORWARD(): return _cmd("MIN_FORWARD", (0, 0, 0))
+def CMD_MIN_BACKWARD(): return _cmd("MIN_BACKWARD", (0, 0, 0))
+def CMD_MAX_FORWARD(): return _cmd("MAX_FORWARD", (0, 0, 0))
+def CMD_MAX_BACKWARD(): return _cmd("MAX_BACKWARD", (0, 0, 0))
+def CMD_CMUL_FORWARD(): return _cmd("CMUL_FORWARD")
+def CMD_CMUL_BACKWARD(): return _cmd("CMUL_BACKWARD")
+def CMD_DATATYPE_CONVERSION_FORWARD(): return _cmd("DATATYPE_CONVERSION_FORWARD", (0, 0, 0))
+def CMD_DATATYPE_CONVERSION_BACKWARD(): return _cmd("DATATYPE_CONVERSION_BACKWARD", (0, 0, 0))
+def CMD_FORMAT_TRANSFORM_BACKWARD(): return _cmd("FORMAT_TRANSFORM_BACKWARD", (0, 0, 0))
+def CMD_COMPRESSION_LSSC_FORWARD(): return _cmd("COMPRESSION_LSSC_FORWARD", (0, 0, 0))
+def CMD_COMPRESSION_LSSC_BACKWARD(): return _cmd("COMPRESSION_LSSC_BACKWARD", (0, 0, 0))
+def CMD_ROI_ALIGN_FORWARD(rows, cols): return _cmd("ROI_ALIGN_FORWARD", (rows, cols, 1))
+def CMD_ROI_ALIGN_BACKWARD(rows, cols): return _cmd("ROI_ALIGN_BACKWARD", (rows, cols, 1))
+
+
+def _clamp(name, lo, hi):
+    """CMD_CLAMP_*(min, max): NaN = no bound on that side (ccv_nnc.h:245-248)."""
+    c = _cmd(name)
+    c.info.clamp.min, c.info.clamp.max = lo, hi
+    return c
+
+
+def CMD_CLAMP_FORWARD(lo, hi): return _clamp("CLAMP_FORWARD", lo, hi)
+def CMD_CLAMP_BACKWARD(lo, hi): return _clamp("CLAMP_BACKWARD", lo, hi)
+def CMD_MASKED_FILL_FORWARD(eq, fill): return _blas_a("MASKED_FILL_FORWARD", eq, fill)
+def CMD_MASKED_FILL_BACKWARD(eq, fill): return _blas_a("MASKED_FILL_BACKWARD", eq, fill)
+
+
+def _transpose(name, axis_a, axis_b):
+    c = _cmd(name)
+    c.info.transpose.axis[0], c.info.transpose.axis[1] = axis_a, axis_b
+    return c
+
+
+def CMD_TRANSPOSE_FORWARD(axis_a, axis_b): return _transpose("TRANSPOSE_FORWARD", axis_a, axis_b)
+def CMD_TRANSPOSE_BACKWARD(axis_a, axis_b): return _transpose("TRANSPOSE_BACKWARD", axis_a, axis_b)
+
+
+def _nms(name, iou_threshold):
+    """CMD_NMS_*(iou_threshold): the macro leaves info.size zero (ccv_nnc_cmd_easy.h:162-164)."""
+    c = _cmd(name, (0, 0, 0))
+    c.info.nms.iou_threshold = iou_threshold
+    return c
+
+
+def CMD_NMS_FORWARD(iou_threshold): return _nms("NMS_FORWARD", iou_threshold)
+def CMD_NMS_BACKWARD(iou_threshold): return _nms("NMS_BACKWARD", iou_threshold)
 
 
 def CMD_GELU_FORWARD(tanh=0):
