@@ -19,23 +19,10 @@ namespace {
 
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// NNC_MI355X_CONV_ALGO_FUSE_RELU (include/nnc_mi355x.h): the forward command in progress on this thread was asked to write
-// max(0, .); a kernel that does so in its epilogue says so, otherwise _conv_forw_any rectifies the output afterwards.
-static thread_local int tl_relu_want = 0, tl_relu_done = 0;
-// ... and on the way back (the same bit on CONVOLUTION_BACKWARD): the data gradient is masked by a > 0, a being the command's forward
-// input -- a ReLU's output.  _conv_back publishes a's NHWC image while the data gradient runs; a kernel that masked as it wrote says so.
-static thread_local int tl_mask_want = 0, tl_mask_done = 0;
-static thread_local Image4 tl_mask = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-static bool mask_fits(const Image4& dst)
-{
-	const Image4& m = tl_mask;
-	return m.p && m.n == dst.n && m.h == dst.h && m.w == dst.w && m.c == dst.c && m.sc == 1 && aligned16(m.p) && m.sw % 4 == 0 && m.sh % 4 == 0 && (m.n == 1 || m.sn % 4 == 0);
-}
-
 // A backward command that computes BOTH gradients (_conv_back) runs its filter gradient first.  Where a pass of the filter gradient reads a tensor that a
 // kernel of the data gradient would read again, it makes that kernel's product on the way and leaves it in the command's workspace, behind everything the
-// filter gradient itself uses (TUNE_CONV_BACK_SHARE; same expressions in the same order: bit-identical).  Lives for ONE command: _conv_back sets the wishes
-// from what the data gradient WILL run, conv_wino_wgrad fills in what it made, the data gradient's launcher takes it if it is there, _conv_back clears.
+// filter gradient itself uses (TUNE_CONV_BACK_SHARE; same expressions in the same order: bit-identical).  _conv_back sets the wishes from what the data
+// gradient WILL run, conv_wino_wgrad fills in what it made, the data gradient's launcher takes it if it is there.
 struct back_share_t {
 	int want_v;         // the data gradient is conv_wino_run<true> on the filter gradient's tile grid, unsliced: its V = B^T g B can come from the pass that makes W = G' g G'^T
 	int want_bits;      // the data gradient is the fused kernel with 2 x 8 tile groups under a ReLU mask, the mask being the map the filter gradient transforms
@@ -44,7 +31,6 @@ struct back_share_t {
 	unsigned* bits;     // made: the mask bits in wino_mask_pack_kernel<2, 8>'s layout, at bits_off
 	size_t v_off, bits_off;
 };
-static thread_local back_share_t tl_share = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
 
 // nnc_mi355x_debug_conv_mask_bits (tests): host memory that the next fused masked data gradient copies its mask bits to, whoever made them
 static void* g_dbg_bits_dst = 0;
@@ -57,6 +43,21 @@ struct conv_geom_t {
 	int kh, kw, Cg, Kg, groups;
 	int sy, sx, pby, pbx, dy, dx;
 };
+
+// The state of ONE command on its way through the layers below (conv_call_t() = a plain command): made by the entry functions, handed down by reference.
+struct conv_call_t {
+	// NNC_MI355X_CONV_ALGO_FUSE_RELU (include/nnc_mi355x.h): the forward command was asked to write max(0, .); a kernel that does so in its epilogue says so,
+	// otherwise conv_forw_entry rectifies the output afterwards.  On the way back (the same bit on CONVOLUTION_BACKWARD) the data gradient is masked by a > 0, a
+	// being the command's forward input -- a ReLU's output: _conv_back alone puts a's NHWC image here (p == 0: no mask); a kernel that masked as it wrote says so.
+	int relu_want, relu_done, mask_want, mask_done;
+	Image4 mask;
+	int staged;         // the command runs on fp32 images of its half or mixed tensors (half_staged_exec): the route such a command had, no depthwise kernels
+	back_share_t share; // _conv_back's, for the one command
+};
+static bool mask_fits(const Image4& m, const Image4& dst)
+{
+	return m.p && m.n == dst.n && m.h == dst.h && m.w == dst.w && m.c == dst.c && m.sc == 1 && aligned16(m.p) && m.sw % 4 == 0 && m.sh % 4 == 0 && (m.n == 1 || m.sn % 4 == 0);
+}
 
 static bool conv_geometry(const ccv_nnc_cmd_t& cmd, const ccv_nnc_hint_t& hint, const Image4& a, const Image4& b, const ccv_nnc_tensor_t* w, conv_geom_t* g)
 {
@@ -140,7 +141,7 @@ static int wino_slice_images(const int N, const int tiles_per_image, const int C
 
 // dst (+ bias) = conv3x3(src, w), stride 1, source padding (pad_y, pad_x);  FLIP: dgrad's mirrored / role-swapped weights.
 template <bool FLIP>
-static int conv_wino_run(const char* name, const conv_geom_t& g, const wino_plan_t& p, const Image4& src, const float* w, const float* bias, const Image4& dst, const int pad_y, const int pad_x, const int flags, ccv_nnc_stream_context_t* const ctx)
+static int conv_wino_run(conv_call_t& call, const char* name, const conv_geom_t& g, const wino_plan_t& p, const Image4& src, const float* w, const float* bias, const Image4& dst, const int pad_y, const int pad_x, const int flags, ccv_nnc_stream_context_t* const ctx)
 {
 	const int Cs = src.c, Cd = dst.c;
 	const int per_image = p.TH * p.TW;
@@ -148,14 +149,15 @@ static int conv_wino_run(const char* name, const conv_geom_t& g, const wino_plan
 	const size_t v_bytes = nb == g.N ? p.v_bytes : (sizeof(float) * 36 * (size_t)nb * per_image * Cs + 255) & ~(size_t)255;
 	const size_t m_bytes = nb == g.N ? p.m_bytes : (sizeof(float) * 36 * (size_t)nb * per_image * Cd + 255) & ~(size_t)255;
 	// (data gradient behind the same command's filter gradient: V is already there -- wino_outgrad_both_kernel -- and U, M go in front of it)
-	bool have_v = FLIP && tl_share.v && nb == g.N && p.u_bytes + m_bytes <= tl_share.v_off;
+	const back_share_t& share = call.share;
+	bool have_v = FLIP && share.v && nb == g.N && p.u_bytes + m_bytes <= share.v_off;
 	size_t need = p.u_bytes + v_bytes + m_bytes;
-	if (have_v && tl_share.v_off + v_bytes > need) need = tl_share.v_off + v_bytes;
+	if (have_v && share.v_off + v_bytes > need) need = share.v_off + v_bytes;
 	char* ws = (char*)workspace_of(ctx, need);
 	if (!ws) return CCV_NNC_EXEC_OOM;
-	if (have_v && (float*)(ws + tl_share.v_off) != tl_share.v) have_v = false; // (the workspace moved: not inside a scope)
+	if (have_v && (float*)(ws + share.v_off) != share.v) have_v = false; // (the workspace moved: not inside a scope)
 	float* const U = (float*)ws;
-	float* const V = have_v ? tl_share.v : (float*)(ws + p.u_bytes);
+	float* const V = have_v ? share.v : (float*)(ws + p.u_bytes);
 	float* const M = have_v ? (float*)(ws + p.u_bytes) : (float*)(ws + p.u_bytes + v_bytes);
 	hipStream_t stream = stream_of(ctx);
 	hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_weight_kernel<FLIP>), dim3(blocks_exact((size_t)Cs * Cd, 256)), dim3(256), 0, stream, w, U, g.K, g.C);
@@ -166,8 +168,8 @@ static int conv_wino_run(const char* name, const conv_geom_t& g, const wino_plan
 		WinoTiles ti;
 		ti.TH = p.TH; ti.TW = p.TW; ti.T = T;
 		ti.H = src.h; ti.W = src.w; ti.sn = src.sn; ti.sh = src.sh; ti.sw = src.sw; ti.oy = -pad_y; ti.ox = -pad_x; ti.C4 = Cs / 4;
-		ti.relu = (!FLIP && tl_relu_want) ? 1 : 0;
-		if (ti.relu) tl_relu_done = 1;
+		ti.relu = (!FLIP && call.relu_want) ? 1 : 0;
+		if (ti.relu) call.relu_done = 1;
 		ti.mask = 0; ti.m_sn = ti.m_sh = ti.m_sw = 0;
 		ti.d_c4.init(ti.C4); ti.d_tw.init(ti.TW); ti.d_th.init(ti.TH);
 		if (!have_v) hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_input_kernel<false>), dim3(blocks_exact((size_t)T * ti.C4, 256)), dim3(256), 0, stream, (const float*)src.p + (long)n0 * src.sn, V, ti, WinoMaskOut());
@@ -181,9 +183,9 @@ static int conv_wino_run(const char* name, const conv_geom_t& g, const wino_plan
 		if (ret != CCV_NNC_EXEC_SUCCESS) return ret;
 		ti.H = dst.h; ti.W = dst.w; ti.sn = dst.sn; ti.sh = dst.sh; ti.sw = dst.sw; ti.C4 = Cd / 4;
 		ti.d_c4.init(ti.C4);
-		if (FLIP && mask_fits(dst)) { // data gradient under a ReLU backward: the output transform reads the map's 16 bytes next to each store
-			ti.mask = tl_mask.p + (long)n0 * tl_mask.sn; ti.m_sn = tl_mask.sn; ti.m_sh = tl_mask.sh; ti.m_sw = tl_mask.sw;
-			tl_mask_done = 1;
+		if (FLIP && mask_fits(call.mask, dst)) { // data gradient under a ReLU backward: the output transform reads the map's 16 bytes next to each store
+			ti.mask = call.mask.p + (long)n0 * call.mask.sn; ti.m_sn = call.mask.sn; ti.m_sh = call.mask.sh; ti.m_sw = call.mask.sw;
+			call.mask_done = 1;
 		}
 		hipLaunchKernelGGL(wino_output_kernel, dim3(blocks_exact((size_t)T * ti.C4, 256)), dim3(256), 0, stream, (const float*)M, bias, dst.p + (long)n0 * dst.sn, ti);
 		HIP_ENFORCE(hipGetLastError());
@@ -228,9 +230,9 @@ static size_t wino_fused_scratch_bound(const int Kout, const int Cred)
 }
 
 // ... and its mask bits (data gradient under a ReLU backward): 1 KB per (tile group, 32-channel block) of the gradient written
-static size_t wino_fused_mask_bound(const conv_geom_t& g)
+static size_t wino_fused_mask_bound(const conv_call_t& call, const conv_geom_t& g)
 {
-	if (!tl_mask_want) return 0;
+	if (!call.mask_want) return 0;
 	const long TH = (g.H + 3) / 4, TW = (g.W + 3) / 4;
 	long most = 0;
 	static const int shapes[3][2] = { { 4, 4 }, { 2, 8 }, { 8, 2 } };
@@ -242,27 +244,28 @@ static size_t wino_fused_mask_bound(const conv_geom_t& g)
 }
 
 template <bool FLIP>
-static int conv_wino_fused_run(const char* name, const conv_geom_t& g, const wino_fused_plan_t& p, const Image4& src, const float* w, const float* bias, const Image4& dst, const int pad_y, const int pad_x, ccv_nnc_stream_context_t* const ctx)
+static int conv_wino_fused_run(conv_call_t& call, const char* name, const conv_geom_t& g, const wino_fused_plan_t& p, const Image4& src, const float* w, const float* bias, const Image4& dst, const int pad_y, const int pad_x, ccv_nnc_stream_context_t* const ctx)
 {
 	// data gradient under a ReLU backward: the mask as bits in the epilogue's order, packed first (1 / 32 of the map; no room: unmasked, the caller's pass follows)
-	size_t bits_bytes = FLIP && mask_fits(dst) && (long)p.groups * p.KB <= 0x7fffffffL ? (size_t)p.groups * p.KB * 1024 : 0;
+	const back_share_t& share = call.share;
+	size_t bits_bytes = FLIP && mask_fits(call.mask, dst) && (long)p.groups * p.KB <= 0x7fffffffL ? (size_t)p.groups * p.KB * 1024 : 0;
 	// (behind the same command's filter gradient the bits may be there already: wino_input_kernel<true> wrote them next to V)
-	bool have_bits = FLIP && bits_bytes && tl_share.bits && p.GH == 2 && p.GYn == tl_share.GYn && p.GXn == tl_share.GXn && p.KB == tl_share.KB && p.uf_bytes <= tl_share.bits_off;
-	float* UF = (float*)workspace_of(ctx, have_bits ? tl_share.bits_off + bits_bytes : p.uf_bytes + bits_bytes);
-	if (have_bits && (!UF || (unsigned*)((char*)UF + tl_share.bits_off) != tl_share.bits)) { have_bits = false; UF = (float*)workspace_of(ctx, p.uf_bytes + bits_bytes); }
+	bool have_bits = FLIP && bits_bytes && share.bits && p.GH == 2 && p.GYn == share.GYn && p.GXn == share.GXn && p.KB == share.KB && p.uf_bytes <= share.bits_off;
+	float* UF = (float*)workspace_of(ctx, have_bits ? share.bits_off + bits_bytes : p.uf_bytes + bits_bytes);
+	if (have_bits && (!UF || (unsigned*)((char*)UF + share.bits_off) != share.bits)) { have_bits = false; UF = (float*)workspace_of(ctx, p.uf_bytes + bits_bytes); }
 	if (!UF && bits_bytes) { bits_bytes = 0; UF = (float*)workspace_of(ctx, p.uf_bytes); }
 	if (!UF) return CCV_NNC_EXEC_OOM;
 	hipStream_t stream = stream_of(ctx);
-	unsigned* const bits = have_bits ? tl_share.bits : (bits_bytes ? (unsigned*)((char*)UF + p.uf_bytes) : 0);
-	if (have_bits) tl_mask_done = 1;
+	unsigned* const bits = have_bits ? share.bits : (bits_bytes ? (unsigned*)((char*)UF + p.uf_bytes) : 0);
+	if (have_bits) call.mask_done = 1;
 	else if (bits) {
 		const dim3 grid((unsigned)((long)p.groups * p.KB));
-		const Image4& m = tl_mask;
+		const Image4& m = call.mask;
 		if (p.GH == 4) hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_mask_pack_kernel<4, 4>), grid, dim3(256), 0, stream, (const float*)m.p, m.sn, m.sh, m.sw, bits, dst.h, dst.w, dst.c, p.GYn, p.GXn, p.KB);
 		else if (p.GH == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_mask_pack_kernel<2, 8>), grid, dim3(256), 0, stream, (const float*)m.p, m.sn, m.sh, m.sw, bits, dst.h, dst.w, dst.c, p.GYn, p.GXn, p.KB);
 		else hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_mask_pack_kernel<8, 2>), grid, dim3(256), 0, stream, (const float*)m.p, m.sn, m.sh, m.sw, bits, dst.h, dst.w, dst.c, p.GYn, p.GXn, p.KB);
 		HIP_ENFORCE(hipGetLastError());
-		tl_mask_done = 1;
+		call.mask_done = 1;
 	}
 	if (bits && g_dbg_bits_dst) {
 		g_dbg_bits_got = (size_t)p.groups * p.KB * 1024;
@@ -289,8 +292,8 @@ static int conv_wino_fused_run(const char* name, const conv_geom_t& g, const win
 	if (wgs < 8 * team) wgs = 8 * team;
 	const unsigned grid = (unsigned)(wgs / (8 * team) * (8 * team));
 	a.team = team;
-	a.relu = (!FLIP && tl_relu_want) ? 1 : 0;
-	if (a.relu) tl_relu_done = 1;
+	a.relu = (!FLIP && call.relu_want) ? 1 : 0;
+	if (a.relu) call.relu_done = 1;
 	a.mask_bits = bits;
 	note_kernel(name);
 	char prof_name[96];
@@ -360,27 +363,28 @@ static bool wino_wgrad_plan(const conv_geom_t& g, wino_wgrad_plan_t* p)
 
 // dbias != 0: also produce the bias gradient (column sums of gr) inside the output-gradient transform; *bias_done tells the
 // caller whether that happened (it needs (K / 4) | 256).
-static int conv_wino_wgrad(const conv_geom_t& g, const wino_wgrad_plan_t& p, const Image4& gr, const Image4& a, float* dw, float* dbias, bool* bias_done, const int flags, ccv_nnc_stream_context_t* const ctx)
+static int conv_wino_wgrad(conv_call_t& call, const conv_geom_t& g, const wino_wgrad_plan_t& p, const Image4& gr, const Image4& a, float* dw, float* dbias, bool* bias_done, const int flags, ccv_nnc_stream_context_t* const ctx)
 {
 	// [ head: nested calls' scratch (they take the workspace base) | V | W | dU | per-block column sums ]
 	// (sized for the whole batch: a slice -- TUNE_WINO_SLICE_KB -- uses the front of each region)
-	// [ ... | the data gradient's V or mask bits ]: what this command's data gradient finds ready (tl_share; only unsliced, so ONE pass below makes all of it)
+	// [ ... | the data gradient's V or mask bits ]: what this command's data gradient finds ready (call.share; only unsliced, so ONE pass below makes all of it)
+	back_share_t& share = call.share;
 	const int per_image = p.t.TH * p.t.TW;
 	const int nb = wino_slice_images(g.N, per_image, g.C, g.K);
-	const size_t bits_bytes = (size_t)g.N * tl_share.GYn * tl_share.GXn * tl_share.KB * 1024;
+	const size_t bits_bytes = (size_t)g.N * share.GYn * share.GXn * share.KB * 1024;
 	const bool fuse_bias = dbias && 256 % (g.K / 4) == 0;
-	const size_t extra = nb != g.N ? 0 : (tl_share.want_v ? (fuse_bias ? p.w_bytes : 0) : (tl_share.want_bits ? bits_bytes : 0)); // (the one-pass kernel exists with the bias sums only: winograd.h)
+	const size_t extra = nb != g.N ? 0 : (share.want_v ? (fuse_bias ? p.w_bytes : 0) : (share.want_bits ? bits_bytes : 0)); // (the one-pass kernel exists with the bias sums only: winograd.h)
 	char* ws = (char*)workspace_of(ctx, p.total() + extra);
 	if (!ws) return CCV_NNC_EXEC_OOM;
-	float* const Vg = extra && tl_share.want_v ? (float*)(ws + p.total()) : 0; // as large as W: 36 x T x K
-	unsigned* const bits = extra && tl_share.want_bits ? (unsigned*)(ws + p.total()) : 0;
+	float* const Vg = extra && share.want_v ? (float*)(ws + p.total()) : 0; // as large as W: 36 x T x K
+	unsigned* const bits = extra && share.want_bits ? (unsigned*)(ws + p.total()) : 0;
 	float* const V = (float*)(ws + p.head_bytes);
 	float* const W = (float*)(ws + p.head_bytes + p.t.v_bytes);
 	float* const dU = (float*)(ws + p.head_bytes + p.t.v_bytes + p.w_bytes);
 	float* const BP = (float*)(ws + p.head_bytes + p.t.v_bytes + p.w_bytes + p.du_bytes);
 	const int acc = (flags & CCV_NNC_ACCUMULATE_OUTPUT) ? 1 : 0;
 	hipStream_t stream = stream_of(ctx);
-	if (bits && (tl_share.GYn * 2 != p.t.TH || tl_share.GXn * 8 != p.t.TW || g.C % WF_KT)) { // tile groups beyond the tile grid, channels beyond C: zeros, and no thread below owns them
+	if (bits && (share.GYn * 2 != p.t.TH || share.GXn * 8 != p.t.TW || g.C % WF_KT)) { // tile groups beyond the tile grid, channels beyond C: zeros, and no thread below owns them
 		const int r = fill_f32((float*)bits, bits_bytes / sizeof(float), 0.f, ctx);
 		if (r != CCV_NNC_EXEC_SUCCESS) return r;
 	}
@@ -393,9 +397,9 @@ static int conv_wino_wgrad(const conv_geom_t& g, const wino_wgrad_plan_t& p, con
 		ti.d_c4.init(ti.C4); ti.d_tw.init(ti.TW); ti.d_th.init(ti.TH);
 		if (bits) { // (padding 1: the 4x4 pixels of tile t are the middle of its patch)
 			WinoMaskOut mo;
-			mo.bits = (unsigned char*)bits; mo.GYn = tl_share.GYn; mo.GXn = tl_share.GXn; mo.KB = tl_share.KB;
+			mo.bits = (unsigned char*)bits; mo.GYn = share.GYn; mo.GXn = share.GXn; mo.KB = share.KB;
 			hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_input_kernel<true>), dim3(blocks_exact((size_t)T * ti.C4, 256)), dim3(256), 0, stream, (const float*)a.p + (long)n0 * a.sn, V, ti, mo);
-			tl_share.bits = bits; tl_share.bits_off = p.total();
+			share.bits = bits; share.bits_off = p.total();
 			__atomic_fetch_add(&g_back_shared[1], 1L, __ATOMIC_RELAXED);
 		} else hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_input_kernel<false>), dim3(blocks_exact((size_t)T * ti.C4, 256)), dim3(256), 0, stream, (const float*)a.p + (long)n0 * a.sn, V, ti, WinoMaskOut());
 		HIP_ENFORCE(hipGetLastError());
@@ -406,7 +410,7 @@ static int conv_wino_wgrad(const conv_geom_t& g, const wino_wgrad_plan_t& p, con
 		if (Vg) { // one pass over the gradient for both of its transforms (the data gradient's patch of tile t starts one pixel up and left of the tile)
 			ti.oy = -1; ti.ox = -1;
 			hipLaunchKernelGGL(wino_outgrad_both_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, grs, Vg, W, ti, BP);
-			tl_share.v = Vg; tl_share.v_off = p.total();
+			share.v = Vg; share.v_off = p.total();
 			__atomic_fetch_add(&g_back_shared[0], 1L, __ATOMIC_RELAXED);
 		} else if (fuse_bias) hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_outgrad_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, stream, grs, W, ti, BP);
 		else hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_outgrad_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, stream, grs, W, ti, (float*)0);
@@ -538,12 +542,12 @@ static void conv_c3_args(const conv_geom_t& g, const Image4& a, const float* w, 
 	c->d_gpr.init(c->groups_per_row); c->d_oh.init(g.OH);
 	c->b_image_bytes = (unsigned)((((long)b.h - 1) * b.sh + ((long)b.w - 1) * b.sw + b.c) * 4);
 }
-static int conv_c3_forw(const conv_geom_t& g, const Image4& a, const float* w, const float* bias, const Image4& b, ccv_nnc_stream_context_t* const ctx)
+static int conv_c3_forw(conv_call_t& call, const conv_geom_t& g, const Image4& a, const float* w, const float* bias, const Image4& b, ccv_nnc_stream_context_t* const ctx)
 {
 	ConvC3Args c;
 	conv_c3_args(g, a, w, bias, b, &c);
-	c.relu = tl_relu_want ? 1 : 0;
-	if (c.relu) tl_relu_done = 1;
+	c.relu = call.relu_want ? 1 : 0;
+	if (c.relu) call.relu_done = 1;
 	hipStream_t stream = stream_of(ctx);
 	const long want = ((long)c.groups + 3) / 4, cap = (long)device_cu_count() * 8;
 	const unsigned grid = (unsigned)(want < cap ? want : cap);
@@ -580,18 +584,18 @@ static int conv_c3_wgrad(const conv_geom_t& g, const Image4& gr, const Image4& a
 	return CCV_NNC_EXEC_SUCCESS;
 }
 
-static int conv_forw_nhwc(const conv_geom_t& g, const Image4& a, const float* w, const float* bias, const Image4& b, const int algo, const int flags, ccv_nnc_stream_context_t* const ctx)
+static int conv_forw_nhwc(conv_call_t& call, const conv_geom_t& g, const Image4& a, const float* w, const float* bias, const Image4& b, const int algo, const int flags, ccv_nnc_stream_context_t* const ctx)
 {
 	if (a.sc != 1 || !pixel_linear(b) || !image_fits_int(a)) return CCV_NNC_EXEC_INVALID;
-	if (algo != CONV_ALGO_IMPLICIT_GEMM && conv_c3_ok(g, a, b)) return conv_c3_forw(g, a, w, bias, b, ctx);
+	if (algo != CONV_ALGO_IMPLICIT_GEMM && conv_c3_ok(g, a, b)) return conv_c3_forw(call, g, a, w, bias, b, ctx);
 	wino_plan_t wp;
 	wino_fused_plan_t fp;
 	if (algo != CONV_ALGO_IMPLICIT_GEMM && algo != CONV_ALGO_WINOGRAD && g.pby <= 2 && g.pbx <= 2 && g.pby >= 0 && g.pbx >= 0 && wino_fused_plan(g, a, b, &fp) && (algo == CONV_ALGO_WINOGRAD_FUSED || wino_fused_preferred(g.C, fp, b))) {
-		const int r = conv_wino_fused_run<false>("conv_fwd_wino_fused", g, fp, a, w, bias, b, g.pby, g.pbx, ctx);
+		const int r = conv_wino_fused_run<false>(call, "conv_fwd_wino_fused", g, fp, a, w, bias, b, g.pby, g.pbx, ctx);
 		if (r != CCV_NNC_EXEC_OOM) return r;
 	}
 	if (algo != CONV_ALGO_IMPLICIT_GEMM && wino_plan(g, g.OH, g.OW, g.C, g.K, &wp) && wino_images_ok(a, b, w, bias) && (algo >= CONV_ALGO_WINOGRAD || wino_preferred(wp, g.C, g.K))) {
-		const int r = conv_wino_run<false>("conv_fwd_wino", g, wp, a, w, bias, b, g.pby, g.pbx, flags, ctx);
+		const int r = conv_wino_run<false>(call, "conv_fwd_wino", g, wp, a, w, bias, b, g.pby, g.pbx, flags, ctx);
 		if (r != CCV_NNC_EXEC_OOM) return r; // the transformed images did not fit the device: the implicit GEMM needs no such scratch
 	}
 	const long M = (long)g.N * g.OH * g.OW;
@@ -671,7 +675,6 @@ static size_t conv_dgrad_parity_scratch(const conv_geom_t& g)
 	if (!conv_dgrad_parity_ok(g)) return 0;
 	return conv_dgrad_parity_prefix(g) + gemm_workspace_bound((long)g.N * ((g.H + 1) / 2) * ((g.W + 1) / 2), g.C, (long)((g.kh + 1) / 2) * ((g.kw + 1) / 2) * g.K) + 256;
 }
-static int conv_forw_nhwc(const conv_geom_t& g, const Image4& a, const float* w, const float* bias, const Image4& b, const int algo, const int flags, ccv_nnc_stream_context_t* const ctx);
 static int conv_dgrad_parity(const conv_geom_t& g, const Image4& gr, const float* w, const Image4& h, const int flags, ccv_nnc_stream_context_t* const ctx)
 {
 	const int U0 = (g.H + 1) / 2, V0 = (g.W + 1) / 2;
@@ -705,7 +708,8 @@ static int conv_dgrad_parity(const conv_geom_t& g, const Image4& gr, const float
 				q.kh = ny; q.kw = nx; q.Cg = g.K; q.Kg = g.C; q.groups = 1; q.sy = 1; q.sx = 1; q.pby = pb_y; q.pbx = pb_x; q.dy = 1; q.dx = 1;
 				Image4 ti;
 				ti.p = T; ti.n = g.N; ti.h = U; ti.w = V; ti.c = g.C; ti.sc = 1; ti.sw = g.C; ti.sh = (long)V * g.C; ti.sn = (long)U * V * g.C;
-				const int r = conv_forw_nhwc(q, gr, Fw, 0, ti, CONV_ALGO_IMPLICIT_GEMM, flags & ~CCV_NNC_ACCUMULATE_OUTPUT, ctx);
+				conv_call_t plain = conv_call_t(); // (a forward contraction on the way back: nothing of the backward command's state is its)
+				const int r = conv_forw_nhwc(plain, q, gr, Fw, 0, ti, CONV_ALGO_IMPLICIT_GEMM, flags & ~CCV_NNC_ACCUMULATE_OUTPUT, ctx);
 				if (r != CCV_NNC_EXEC_SUCCESS) return r;
 			}
 			hipLaunchKernelGGL(parity_scatter_kernel, dim3(grid_for(cells, 256)), dim3(256), 0, stream, (const float*)T, h.p, U, V, vec ? g.C / 4 : -g.C, h.sn, h.sh, h.sw, py, px, cells);
@@ -714,7 +718,7 @@ static int conv_dgrad_parity(const conv_geom_t& g, const Image4& gr, const float
 	return CCV_NNC_EXEC_SUCCESS;
 }
 
-// which Winograd form the data gradient takes first (conv_dgrad_nhwc; _conv_back asks ahead of the filter gradient: tl_share)
+// which Winograd form the data gradient takes first (conv_dgrad_nhwc; _conv_back asks ahead of the filter gradient: call.share)
 static bool conv_dgrad_takes_fused(const conv_geom_t& g, const Image4& gr, const Image4& h, const int algo, wino_fused_plan_t* fp)
 {
 	return algo != CONV_ALGO_IMPLICIT_GEMM && algo != CONV_ALGO_WINOGRAD && g.pby <= 2 && g.pbx <= 2 && g.pby >= 0 && g.pbx >= 0 && wino_fused_plan(g, gr, h, fp) && (algo == CONV_ALGO_WINOGRAD_FUSED || wino_fused_preferred(g.K, *fp, h));
@@ -724,17 +728,17 @@ static bool conv_dgrad_takes_wino(const conv_geom_t& g, const Image4& gr, const 
 	return algo != CONV_ALGO_IMPLICIT_GEMM && wino_plan(g, g.H, g.W, g.K, g.C, wp) && wino_images_ok(gr, h, w, 0) && (algo >= CONV_ALGO_WINOGRAD || wino_preferred(*wp, g.K, g.C));
 }
 
-static int conv_dgrad_nhwc(const conv_geom_t& g, const Image4& gr, const float* w, const Image4& h, const int algo, const int flags, ccv_nnc_stream_context_t* const ctx)
+static int conv_dgrad_nhwc(conv_call_t& call, const conv_geom_t& g, const Image4& gr, const float* w, const Image4& h, const int algo, const int flags, ccv_nnc_stream_context_t* const ctx)
 {
 	if (gr.sc != 1 || !pixel_linear(h) || !image_fits_int(gr)) return CCV_NNC_EXEC_INVALID;
 	wino_plan_t wp;
 	wino_fused_plan_t fp;
 	if (conv_dgrad_takes_fused(g, gr, h, algo, &fp)) {
-		const int r = conv_wino_fused_run<true>("conv_dgrad_wino_fused", g, fp, gr, w, 0, h, 2 - g.pby, 2 - g.pbx, ctx);
+		const int r = conv_wino_fused_run<true>(call, "conv_dgrad_wino_fused", g, fp, gr, w, 0, h, 2 - g.pby, 2 - g.pbx, ctx);
 		if (r != CCV_NNC_EXEC_OOM) return r;
 	}
 	if (conv_dgrad_takes_wino(g, gr, w, h, algo, &wp)) {
-		const int r = conv_wino_run<true>("conv_dgrad_wino", g, wp, gr, w, 0, h, 2 - g.pby, 2 - g.pbx, flags, ctx);
+		const int r = conv_wino_run<true>(call, "conv_dgrad_wino", g, wp, gr, w, 0, h, 2 - g.pby, 2 - g.pbx, flags, ctx);
 		if (r != CCV_NNC_EXEC_OOM) return r;
 	}
 	if (algo != CONV_ALGO_IMPLICIT_GEMM && !(flags & CCV_NNC_ACCUMULATE_OUTPUT) && conv_dgrad_parity_ok(g) && g.kh * g.kw > 1) {
@@ -782,7 +786,7 @@ static bool conv_wgrad_takes_wino(const conv_geom_t& g, const Image4& gr, const 
 }
 
 // dw[k,i,j,c] (+)= sum_{n,y,x} g[n,y,x,k] * a[n, y*s-p+i*d, x*s-p+j*d, c]
-static int conv_wgrad_nhwc(const conv_geom_t& g, const Image4& gr, const Image4& a, float* dw, float* dbias, bool* bias_done, const int algo, const int flags, ccv_nnc_stream_context_t* const ctx)
+static int conv_wgrad_nhwc(conv_call_t& call, const conv_geom_t& g, const Image4& gr, const Image4& a, float* dw, float* dbias, bool* bias_done, const int algo, const int flags, ccv_nnc_stream_context_t* const ctx)
 {
 	if (bias_done) *bias_done = false;
 	if (a.sc != 1 || !pixel_linear(gr) || !image_fits_int(a)) return CCV_NNC_EXEC_INVALID;
@@ -798,7 +802,7 @@ static int conv_wgrad_nhwc(const conv_geom_t& g, const Image4& gr, const Image4&
 	}
 	wino_wgrad_plan_t wp;
 	if (conv_wgrad_takes_wino(g, gr, a, dw, algo, &wp)) {
-		const int r = conv_wino_wgrad(g, wp, gr, a, dw, dbias, bias_done, flags, ctx);
+		const int r = conv_wino_wgrad(call, g, wp, gr, a, dw, dbias, bias_done, flags, ctx);
 		if (r != CCV_NNC_EXEC_OOM) return r;
 	}
 	const long P = (long)g.N * g.OH * g.OW;
@@ -823,6 +827,25 @@ static int conv_wgrad_nhwc(const conv_geom_t& g, const Image4& gr, const Image4&
 	if (vec) CONV_WGRAD(true, false);
 	else CONV_WGRAD(false, false);
 #undef CONV_WGRAD
+}
+
+// ---- the tensor lists of the two commands, unpacked (absent = 0; what a route demands of them is the route's own check) ---------------------------
+struct conv_forw_args_t { const ccv_nnc_tensor_t *a, *w, *bias; ccv_nnc_tensor_t* b; };
+static conv_forw_args_t conv_forw_unpack(ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
+{
+	return { input_size > 0 ? inputs[0] : 0, input_size > 1 ? inputs[1] : 0, input_size > 2 ? inputs[2] : 0, output_size > 0 ? outputs[0] : 0 };
+}
+// inputs: gradient g, forward input a, [w]; outputs: [h], [dw], [dbias]   (ccv_nnc_convolution.c:16-37)
+struct conv_back_args_t {
+	const ccv_nnc_tensor_t *gt, *a, *w;
+	ccv_nnc_tensor_t *h, *dw, *dbias;
+	const ccv_nnc_tensor_t *shape_src, *wshape; // who has the forward input's shape (a, else h) and the filter's (dw, else w)
+};
+static conv_back_args_t conv_back_unpack(ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
+{
+	conv_back_args_t t = { input_size > 0 ? inputs[0] : 0, input_size > 1 ? inputs[1] : 0, input_size > 2 ? inputs[2] : 0, output_size > 0 ? outputs[0] : 0, output_size > 1 ? outputs[1] : 0, output_size > 2 ? outputs[2] : 0, 0, 0 };
+	t.shape_src = t.a ? t.a : t.h; t.wshape = t.dw ? t.dw : t.w;
+	return t;
 }
 
 // ---- 1x1 convolutions on NCHW tensors: plain batched GEMMs over the tensors WHERE THEY LIE ------------------------------------
@@ -877,12 +900,12 @@ static int conv1x1_nchw_forw(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint,
 }
 
 template <class T>
-static int conv1x1_nchw_back(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, const ccv_nnc_tensor_t* g, const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* w, ccv_nnc_tensor_t* h, ccv_nnc_tensor_t* dw, ccv_nnc_tensor_t* dbias, ccv_nnc_stream_context_t* const ctx)
+static int conv1x1_nchw_back(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, const conv_back_args_t& t, ccv_nnc_stream_context_t* const ctx)
 {
 	typedef typename conv1x1_types<T>::Out Out;
+	const auto [g, a, w, h, dw, dbias, shape_src, wshape] = t;
 	int N, K, P;
 	if (!conv1x1_cmd_ok(cmd, hint) || !nchw_dense(g, &N, &K, &P) || K != cmd.info.convolution.count) return CCV_NNC_EXEC_NO_KERNEL;
-	const ccv_nnc_tensor_t* shape_src = a ? a : h;
 	int Na, C, Pa;
 	if (!shape_src || !nchw_dense(shape_src, &Na, &C, &Pa) || Na != N || Pa != P) return CCV_NNC_EXEC_NO_KERNEL;
 	if (h && (!nchw_dense(h, &Na, &C, &Pa) || Na != N || Pa != P || !w || !tensor_contiguous(w) || (long)tensor_count(w->info) != (long)K * C)) return CCV_NNC_EXEC_NO_KERNEL;
@@ -945,7 +968,6 @@ static void dense_nhwc_like(const ccv_nnc_tensor_t* like, const Image4& li, floa
 // (and, in NCHW, between layout passes) it used almost none of the machine.  Taken (TUNE_CONV_DEPTHWISE) when every tensor is dense, of the one element
 // type T and -- activations -- of one format, on 16-byte aligned bases, with C a whole number of 16-byte vectors where channels are innermost; everything
 // else (views, mixed precision, channel multipliers, odd channel counts in NHWC) keeps the route it had.  CCV_NNC_EXEC_NO_KERNEL = not this path.
-static thread_local int tl_dw_staged = 0; // the command in progress runs on fp32 images of its tensors (half_staged_exec)
 template <class T> struct conv_dw_type;
 template <> struct conv_dw_type<float> { enum { datatype = CCV_32F }; };
 template <> struct conv_dw_type<half_t> { enum { datatype = CCV_16F }; };
@@ -958,9 +980,9 @@ static bool conv_dw_dense(const ccv_nnc_tensor_t* t)
 
 // in / out: the forward input's and output's shapes (tensors of the command that have them); *nhwc: the activations' format
 template <class T>
-static bool conv_dw_eligible(const ccv_nnc_cmd_t& cmd, const ccv_nnc_hint_t& hint, const ccv_nnc_tensor_t* in, const ccv_nnc_tensor_t* out, const ccv_nnc_tensor_t* wshape, conv_geom_t* g, bool* nhwc)
+static bool conv_dw_eligible(const conv_call_t& call, const ccv_nnc_cmd_t& cmd, const ccv_nnc_hint_t& hint, const ccv_nnc_tensor_t* in, const ccv_nnc_tensor_t* out, const ccv_nnc_tensor_t* wshape, conv_geom_t* g, bool* nhwc)
 {
-	if (!tune(TUNE_CONV_DEPTHWISE) || tl_dw_staged || cmd.algorithm == CONV_ALGO_IMPLICIT_GEMM || !in || !out || !wshape) return false;
+	if (!tune(TUNE_CONV_DEPTHWISE) || call.staged || cmd.algorithm == CONV_ALGO_IMPLICIT_GEMM || !in || !out || !wshape) return false;
 	if (in->info.format != out->info.format || (in->info.format != CCV_TENSOR_FORMAT_NHWC && in->info.format != CCV_TENSOR_FORMAT_NCHW)) return false;
 	Image4 ii, oi;
 	if (!image4(in, &ii) || !image4(out, &oi) || !conv_geometry(cmd, hint, ii, oi, 0, g)) return false;
@@ -1132,26 +1154,25 @@ static int conv_dw_wgrad(const bool nhwc, const DwGeom& d, const T* gr, const T*
 }
 
 template <class T>
-static int conv_dw_forw(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* w, const ccv_nnc_tensor_t* bias, ccv_nnc_tensor_t* b, ccv_nnc_stream_context_t* const ctx)
+static int conv_dw_forw(const conv_call_t& call, const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* w, const ccv_nnc_tensor_t* bias, ccv_nnc_tensor_t* b, ccv_nnc_stream_context_t* const ctx)
 {
 	conv_geom_t g;
 	bool nhwc;
-	if ((flags & CCV_NNC_ACCUMULATE_OUTPUT) || !conv_dw_eligible<T>(cmd, hint, a, b, w, &g, &nhwc)) return CCV_NNC_EXEC_NO_KERNEL;
+	if ((flags & CCV_NNC_ACCUMULATE_OUTPUT) || !conv_dw_eligible<T>(call, cmd, hint, a, b, w, &g, &nhwc)) return CCV_NNC_EXEC_NO_KERNEL;
 	if (!conv_dw_tensor_ok<T>(a) || !conv_dw_tensor_ok<T>(b) || !conv_dw_dense<T>(w) || (bias && (!conv_dw_dense<T>(bias) || (int)tensor_count(bias->info) != g.C))) return CCV_NNC_EXEC_NO_KERNEL;
 	DwGeom d;
 	conv_dw_geom(g, &d);
-	// (NNC_MI355X_CONV_ALGO_FUSE_RELU: tl_relu_done stays 0 -- the in-place pass of conv_forw_entry follows, the bits are the unfused pair's by construction)
+	// (NNC_MI355X_CONV_ALGO_FUSE_RELU: call.relu_done stays 0 -- the in-place pass of conv_forw_entry follows, the bits are the unfused pair's by construction)
 	return conv_dw_stencil<T>("conv_dw_fwd", nhwc, d, (const T*)a->data.u8, (const T*)w->data.u8, bias ? (const T*)bias->data.u8 : 0, (T*)b->data.u8, ctx);
 }
 
 template <class T>
-static int conv_dw_back(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, const ccv_nnc_tensor_t* gt, const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* w, ccv_nnc_tensor_t* h, ccv_nnc_tensor_t* dw, ccv_nnc_tensor_t* dbias, ccv_nnc_stream_context_t* const ctx)
+static int conv_dw_back(const conv_call_t& call, const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, const conv_back_args_t& t, ccv_nnc_stream_context_t* const ctx)
 {
-	const ccv_nnc_tensor_t* const shape_src = a ? a : h;
-	const ccv_nnc_tensor_t* const wshape = dw ? dw : w;
+	const auto [gt, a, w, h, dw, dbias, shape_src, wshape] = t;
 	conv_geom_t g;
 	bool nhwc;
-	if (!conv_dw_eligible<T>(cmd, hint, shape_src, gt, wshape, &g, &nhwc)) return CCV_NNC_EXEC_NO_KERNEL;
+	if (!conv_dw_eligible<T>(call, cmd, hint, shape_src, gt, wshape, &g, &nhwc)) return CCV_NNC_EXEC_NO_KERNEL;
 	if (!conv_dw_tensor_ok<T>(gt) || !conv_dw_tensor_ok<T>(a) || !conv_dw_tensor_ok<T>(h) || (w && !conv_dw_dense<T>(w)) || (dw && !conv_dw_dense<T>(dw)) || (dbias && (!conv_dw_dense<T>(dbias) || (int)tensor_count(dbias->info) != g.C))) return CCV_NNC_EXEC_NO_KERNEL;
 	if ((dw && !a) || (h && !w) || (a && a->info.format != gt->info.format) || (h && h->info.format != gt->info.format)) return CCV_NNC_EXEC_NO_KERNEL;
 	if (w && dw && w->info.format != dw->info.format) return CCV_NNC_EXEC_NO_KERNEL;
@@ -1167,22 +1188,19 @@ static int conv_dw_back(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, cons
 	if (dbias && !a) return CCV_NNC_EXEC_NO_KERNEL; // (a bias gradient alone, without the forward input: the column sums of the other route)
 	int ret;
 	if ((dw || dbias) && (ret = conv_dw_wgrad<T>(nhwc, d, (const T*)gt->data.u8, (const T*)a->data.u8, dw ? (T*)dw->data.u8 : 0, dbias ? (T*)dbias->data.u8 : 0, (flags & CCV_NNC_ACCUMULATE_OUTPUT) ? 1 : 0, ctx)) != CCV_NNC_EXEC_SUCCESS) return ret;
-	// (a masked data gradient -- tl_mask_want -- is left to conv_back_entry's relu_back_inplace)
+	// (a masked data gradient -- call.mask_want -- is left to conv_back_entry's relu_back_inplace)
 	if (h && (ret = conv_dw_stencil<T>("conv_dw_dgrad", nhwc, dd, (const T*)gt->data.u8, (const T*)w->data.u8, (const T*)0, (T*)h->data.u8, ctx)) != CCV_NNC_EXEC_SUCCESS) return ret;
 	return CCV_NNC_EXEC_SUCCESS;
 }
 
-static int _conv_forw(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
+static int _conv_forw(conv_call_t& call, const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
 {
-	if (input_size < 2 || output_size < 1 || !inputs[0] || !inputs[1] || !outputs[0]) return CCV_NNC_EXEC_INVALID;
-	const ccv_nnc_tensor_t* a = inputs[0];
-	const ccv_nnc_tensor_t* w = inputs[1];
-	const ccv_nnc_tensor_t* bias = input_size > 2 ? inputs[2] : 0;
-	ccv_nnc_tensor_t* b = outputs[0];
+	const auto [a, w, bias, b] = conv_forw_unpack(inputs, input_size, outputs, output_size);
+	if (!a || !w || !b) return CCV_NNC_EXEC_INVALID;
 	if (CCV_GET_DATA_TYPE(a->info.datatype) != CCV_32F) return CCV_NNC_EXEC_INVALID;
 	if (a->info.format != b->info.format) return CCV_NNC_EXEC_INVALID;
 	{
-		const int r = conv_dw_forw<float>(cmd, hint, flags, a, w, bias, b, stream_context);
+		const int r = conv_dw_forw<float>(call, cmd, hint, flags, a, w, bias, b, stream_context);
 		if (r != CCV_NNC_EXEC_NO_KERNEL) return r;
 	}
 	if (a->info.format == CCV_TENSOR_FORMAT_NCHW && cmd.algorithm != CONV_ALGO_IMPLICIT_GEMM) {
@@ -1197,7 +1215,7 @@ static int _conv_forw(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const 
 	if (!conv_geometry(cmd, hint, ai, bi, 0, &g) || K != g.K || kh != g.kh || kw != g.kw || Cg != g.Cg) return CCV_NNC_EXEC_INVALID;
 	if (bias && (bias->info.dim[0] != g.K || !tensor_contiguous(bias))) return CCV_NNC_EXEC_INVALID;
 	const bool stage_io = a->info.format == CCV_TENSOR_FORMAT_NCHW, stage_w = w->info.format == CCV_TENSOR_FORMAT_NCHW;
-	if (!stage_io && !stage_w) return conv_forw_nhwc(g, ai, w->data.f32, bias ? bias->data.f32 : 0, bi, cmd.algorithm, flags, stream_context);
+	if (!stage_io && !stage_w) return conv_forw_nhwc(call, g, ai, w->data.f32, bias ? bias->data.f32 : 0, bi, cmd.algorithm, flags, stream_context);
 	const size_t na = stage_io ? align256(sizeof(float) * tensor_count(a->info)) : 0, nb = stage_io ? align256(sizeof(float) * tensor_count(b->info)) : 0;
 	const size_t nw = stage_w ? align256(sizeof(float) * tensor_count(w->info)) : 0;
 	size_t inner = gemm_workspace_bound((long)g.N * g.OH * g.OW, g.Kg, (long)g.kh * g.kw * g.Cg);
@@ -1213,43 +1231,36 @@ static int _conv_forw(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const 
 		if ((ret = weights_nchw_to_nhwc(w->data.f32, (float*)(p + na + nb), g.K, g.Cg, g.kh * g.kw, stream_context)) != CCV_NNC_EXEC_SUCCESS) return ret;
 		wp = (const float*)(p + na + nb);
 	}
-	if (!stage_io) return conv_forw_nhwc(g, ai, wp, bias ? bias->data.f32 : 0, bi, cmd.algorithm, flags, stream_context);
+	if (!stage_io) return conv_forw_nhwc(call, g, ai, wp, bias ? bias->data.f32 : 0, bi, cmd.algorithm, flags, stream_context);
 	ccv_nnc_tensor_t at, bt;
 	dense_nhwc_like(a, ai, (float*)p, &at);
 	dense_nhwc_like(b, bi, (float*)(p + na), &bt);
 	if ((ret = format_transform(a, &at, stream_context)) != CCV_NNC_EXEC_SUCCESS) return ret;
 	Image4 as, bs;
 	image4(&at, &as); image4(&bt, &bs);
-	if ((ret = conv_forw_nhwc(g, as, wp, bias ? bias->data.f32 : 0, bs, cmd.algorithm, flags, stream_context)) != CCV_NNC_EXEC_SUCCESS) return ret;
+	if ((ret = conv_forw_nhwc(call, g, as, wp, bias ? bias->data.f32 : 0, bs, cmd.algorithm, flags, stream_context)) != CCV_NNC_EXEC_SUCCESS) return ret;
 	return format_transform(&bt, b, stream_context);
 }
 
-static int _conv_back(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
+static int _conv_back(conv_call_t& call, const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
 {
-	// inputs: gradient g, forward input a, [w]; outputs: [h], [dw], [dbias]   (ccv_nnc_convolution.c:16-37)
-	if (input_size < 2 || output_size < 1 || !inputs[0]) return CCV_NNC_EXEC_INVALID;
-	const ccv_nnc_tensor_t* gt = inputs[0];
-	const ccv_nnc_tensor_t* a = inputs[1];
-	const ccv_nnc_tensor_t* w = input_size > 2 ? inputs[2] : 0;
-	ccv_nnc_tensor_t* h = outputs[0];
-	ccv_nnc_tensor_t* dw = output_size > 1 ? outputs[1] : 0;
-	ccv_nnc_tensor_t* dbias = output_size > 2 ? outputs[2] : 0;
+	const conv_back_args_t t = conv_back_unpack(inputs, input_size, outputs, output_size);
+	const auto [gt, a, w, h, dw, dbias, shape_src, wshape] = t;
+	if (input_size < 2 || output_size < 1 || !gt) return CCV_NNC_EXEC_INVALID;
 	if (CCV_GET_DATA_TYPE(gt->info.datatype) != CCV_32F) return CCV_NNC_EXEC_INVALID;
 	{
-		const int r = conv_dw_back<float>(cmd, hint, flags, gt, a, w, h, dw, dbias, stream_context);
+		const int r = conv_dw_back<float>(call, cmd, hint, flags, t, stream_context);
 		if (r != CCV_NNC_EXEC_NO_KERNEL) return r;
 	}
 	if (gt->info.format == CCV_TENSOR_FORMAT_NCHW && cmd.algorithm != CONV_ALGO_IMPLICIT_GEMM) {
-		const int r = conv1x1_nchw_back<float>(cmd, hint, flags, gt, a, w, h, dw, dbias, stream_context);
+		const int r = conv1x1_nchw_back<float>(cmd, hint, flags, t, stream_context);
 		if (r != CCV_NNC_EXEC_NO_KERNEL) return r;
 	}
 	Image4 gi;
 	if (!image4(gt, &gi)) return CCV_NNC_EXEC_INVALID;
-	const ccv_nnc_tensor_t* shape_src = a ? a : h; // the forward input's shape
 	if (!shape_src || shape_src->info.format != gt->info.format) return CCV_NNC_EXEC_INVALID;
 	Image4 ai;
 	if (!image4(shape_src, &ai)) return CCV_NNC_EXEC_INVALID;
-	const ccv_nnc_tensor_t* wshape = dw ? dw : w;
 	int K, kh, kw, Cg;
 	if (!weights_shape(wshape, &K, &kh, &kw, &Cg)) return CCV_NNC_EXEC_INVALID;
 	if (w && dw && w->info.format != dw->info.format) return CCV_NNC_EXEC_INVALID;
@@ -1278,13 +1289,13 @@ static int _conv_back(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const 
 	if (dw && cmd.algorithm != CONV_ALGO_IMPLICIT_GEMM && wino_wgrad_plan(g, &wgp) && wgp.total() > inner) inner = wgp.total();
 	wino_wgrad_fused_plan_t wfgp;
 	if (dw && cmd.algorithm != CONV_ALGO_IMPLICIT_GEMM && wino_wgrad_fused_plan(g, &wfgp) && wfgp.total() > inner) inner = wfgp.total();
-	if (h && cmd.algorithm != CONV_ALGO_IMPLICIT_GEMM && wino_fused_scratch_bound(g.C, g.K) + wino_fused_mask_bound(g) > inner) inner = wino_fused_scratch_bound(g.C, g.K) + wino_fused_mask_bound(g);
+	if (h && cmd.algorithm != CONV_ALGO_IMPLICIT_GEMM && wino_fused_scratch_bound(g.C, g.K) + wino_fused_mask_bound(call, g) > inner) inner = wino_fused_scratch_bound(g.C, g.K) + wino_fused_mask_bound(call, g);
 	if (h && cmd.algorithm != CONV_ALGO_IMPLICIT_GEMM && conv_dgrad_parity_scratch(g) > inner) inner = conv_dgrad_parity_scratch(g);
 	if (dw && cmd.algorithm != CONV_ALGO_IMPLICIT_GEMM && g.C == 3 && conv_c3_wgrad_scratch_bound(g.K) > inner) inner = conv_c3_wgrad_scratch_bound(g.K);
 	// Both gradients on the tensors where they lie, the filter gradient via HBM, padding 1 (the 4x4 tiles of the output gradient and of a are the middles of
 	// the data gradient's / the filter gradient's 6x6 patches, on one tile grid), no image slices: what the data gradient needs of a tensor the filter gradient
-	// reads anyway is made in that pass (tl_share) and kept behind the filter gradient's scratch.
-	back_share_t share = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+	// reads anyway is made in that pass (call.share) and kept behind the filter gradient's scratch.
+	back_share_t& share = call.share = back_share_t();
 	const long share_on = tune(TUNE_CONV_BACK_SHARE);
 	if (h && dw && a && w && share_on && !stage_io && !stage_w && g.pby == 1 && g.pbx == 1 && g.OH == g.H && g.OW == g.W && ai.sc == 1 && gi.sc == 1 && pixel_linear(gi) && pixel_linear(hi) && image_fits_int(ai) && image_fits_int(gi)
 		&& !(cmd.algorithm != CONV_ALGO_IMPLICIT_GEMM && conv_c3_ok(g, ai, gi))) {
@@ -1294,19 +1305,16 @@ static int _conv_back(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const 
 		wino_plan_t wp;
 		if (!conv_wgrad_takes_fused(g, gi, ai, dw->data.f32, cmd.algorithm, &wf) && conv_wgrad_takes_wino(g, gi, ai, dw->data.f32, cmd.algorithm, &wg) && wino_slice_images(g.N, wg.t.TH * wg.t.TW, g.C, g.K) == g.N) {
 			if (conv_dgrad_takes_fused(g, gi, hi, cmd.algorithm, &fp)) {
-				tl_mask = ai; // (as below, for mask_fits)
-				if ((share_on & 2) && tl_mask_want && fp.GH == 2 && mask_fits(hi) && (long)fp.groups * fp.KB <= 0x7fffffffL && fp.uf_bytes <= wg.total()) {
+				if ((share_on & 2) && call.mask_want && fp.GH == 2 && mask_fits(ai, hi) && (long)fp.groups * fp.KB <= 0x7fffffffL && fp.uf_bytes <= wg.total()) {
 					share.want_bits = 1; share.GYn = fp.GYn; share.GXn = fp.GXn; share.KB = fp.KB;
 					if (wg.total() + (size_t)fp.groups * fp.KB * 1024 > inner) inner = wg.total() + (size_t)fp.groups * fp.KB * 1024;
 				}
-				tl_mask.p = 0;
 			} else if ((share_on & 1) && dbias && 256 % (g.K / 4) == 0 && conv_dgrad_takes_wino(g, gi, w->data.f32, hi, cmd.algorithm, &wp) && wp.TH == wg.t.TH && wp.TW == wg.t.TW && wp.u_bytes + wp.m_bytes <= wg.total()) {
 				share.want_v = 1;
 				if (wg.total() + wg.w_bytes > inner) inner = wg.total() + wg.w_bytes;
 			}
 		}
 	}
-	struct share_scope_t { share_scope_t(const back_share_t& s) { tl_share = s; } ~share_scope_t() { const back_share_t none = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }; tl_share = none; } } share_scope(share);
 	WorkspaceScope ws(stream_context, ng + na + nh + nw + ndw, inner);
 	char* p = (char*)ws.prefix();
 	if ((ng + na + nh + nw + ndw) && !p) return CCV_NNC_EXEC_OOM;
@@ -1332,7 +1340,7 @@ static int _conv_back(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const 
 			dwp = (float*)(p + ng + na + nh + nw);
 			if (acc && (ret = weights_nchw_to_nhwc(dw->data.f32, dwp, g.K, g.Cg, g.kh * g.kw, stream_context)) != CCV_NNC_EXEC_SUCCESS) return ret;
 		}
-		if ((ret = conv_wgrad_nhwc(g, gim, aim, dwp, dbias ? dbias->data.f32 : 0, &bias_done, cmd.algorithm, flags, stream_context)) != CCV_NNC_EXEC_SUCCESS) return ret;
+		if ((ret = conv_wgrad_nhwc(call, g, gim, aim, dwp, dbias ? dbias->data.f32 : 0, &bias_done, cmd.algorithm, flags, stream_context)) != CCV_NNC_EXEC_SUCCESS) return ret;
 		if (stage_w && (ret = weights_nhwc_to_nchw(dwp, dw->data.f32, g.K, g.Cg, g.kh * g.kw, stream_context)) != CCV_NNC_EXEC_SUCCESS) return ret;
 	}
 	if (dbias && !bias_done) {
@@ -1345,10 +1353,8 @@ static int _conv_back(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const 
 			if ((ret = weights_nchw_to_nhwc(w->data.f32, (float*)(p + ng + na + nh), g.K, g.Cg, g.kh * g.kw, stream_context)) != CCV_NNC_EXEC_SUCCESS) return ret;
 			wp = (const float*)(p + ng + na + nh);
 		}
-		if (tl_mask_want) tl_mask = aim;
-		ret = conv_dgrad_nhwc(g, gim, wp, him, cmd.algorithm, flags, stream_context);
-		tl_mask.p = 0;
-		if (ret != CCV_NNC_EXEC_SUCCESS) return ret;
+		if (call.mask_want) call.mask = aim;
+		if ((ret = conv_dgrad_nhwc(call, g, gim, wp, him, cmd.algorithm, flags, stream_context)) != CCV_NNC_EXEC_SUCCESS) return ret;
 		if (stage_io && (ret = format_transform(&hs, h, stream_context)) != CCV_NNC_EXEC_SUCCESS) return ret;
 	}
 	return CCV_NNC_EXEC_SUCCESS;
@@ -1366,20 +1372,18 @@ static __global__ void __launch_bounds__(256) chan_bias_add_kernel(float* b, con
 }
 static int _conv_transpose_forw(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
 {
-	if (input_size < 2 || output_size < 1 || !inputs[0] || !inputs[1] || !outputs[0]) return CCV_NNC_EXEC_INVALID;
-	ccv_nnc_tensor_t* a = inputs[0];
-	ccv_nnc_tensor_t* w = inputs[1];
-	ccv_nnc_tensor_t* bias = input_size > 2 ? inputs[2] : 0;
-	ccv_nnc_tensor_t* b = outputs[0];
+	const auto [a, w, bias, b] = conv_forw_unpack(inputs, input_size, outputs, output_size);
+	if (!a || !w || !b) return CCV_NNC_EXEC_INVALID;
 	Image4 ai, bi;
 	if (!image4(a, &ai) || !image4(b, &bi) || a->info.format != b->info.format || !tensor_contiguous(b)) return CCV_NNC_EXEC_INVALID;
 	if (bi.c != cmd.info.convolution.count) return CCV_NNC_EXEC_INVALID; // (count sits at the same offset in both parameter structs)
 	ccv_nnc_cmd_t conv = cmd;
 	conv.cmd = CCV_NNC_CONVOLUTION_BACKWARD;
 	conv.info.convolution.count = ai.c; // the convolution whose gradient this is has a's channels as its outputs
-	ccv_nnc_tensor_t* ins[3] = { a, 0, w };
+	ccv_nnc_tensor_t* ins[3] = { inputs[0], 0, inputs[1] };
 	ccv_nnc_tensor_t* outs[1] = { b };
-	const int ret = _conv_back(conv, hint, flags & ~CCV_NNC_ACCUMULATE_OUTPUT, ins, 3, outs, 1, stream_context);
+	conv_call_t call = conv_call_t();
+	const int ret = _conv_back(call, conv, hint, flags & ~CCV_NNC_ACCUMULATE_OUTPUT, ins, 3, outs, 1, stream_context);
 	if (ret != CCV_NNC_EXEC_SUCCESS) return ret;
 	if (bias) {
 		if (!tensor_contiguous(bias) || (int)tensor_count(bias->info) != bi.c) return CCV_NNC_EXEC_INVALID;
@@ -1528,7 +1532,7 @@ static bool conv_nchw_half_f16_ok(const conv_geom_t& g)
 	const long least = tune(TUNE_CONV_NCHW_HALF_F16);
 	return least > 0 && g.groups == 1 && g.Cg >= least && g.Cg % 8 == 0 && g.K % 8 == 0 && (long)g.N * g.OH * g.OW <= 0x7fffffffL && (long)g.N * g.H * g.W <= 0x7fffffffL;
 }
-static int conv_nchw_half_forw(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* w, const ccv_nnc_tensor_t* bias, ccv_nnc_tensor_t* b, ccv_nnc_stream_context_t* const ctx)
+static int conv_nchw_half_forw(conv_call_t& call, const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* w, const ccv_nnc_tensor_t* bias, ccv_nnc_tensor_t* b, ccv_nnc_stream_context_t* const ctx)
 {
 	if ((flags & CCV_NNC_ACCUMULATE_OUTPUT) || w->info.format != CCV_TENSOR_FORMAT_NCHW || !tensor_contiguous(w)) return CCV_NNC_EXEC_NO_KERNEL;
 	int Na, Ca, Pa, Nb, Cb, Pb;
@@ -1543,7 +1547,7 @@ static int conv_nchw_half_forw(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hin
 	int ret;
 	// Enough reduction channels: the f16 implicit GEMM on the matrix cores between HALF transposes (2 + 2 bytes per activation element around the kernel instead
 	// of 6 + 6, and 456-539 TFLOP/s of direct arithmetic against the fp32 Winograd kernels' ~190 direct-equivalent; tools/half_bench.py).  The ReLU a look-ahead
-	// may have asked for is left to its own pass there (tl_relu_done stays clear).
+	// may have asked for is left to its own pass there (call.relu_done stays clear).
 	if (conv_nchw_half_f16_ok(g)) {
 		const size_t ha = align256(sizeof(half_t) * tensor_count(a->info)), hb = align256(sizeof(half_t) * tensor_count(b->info)), hw = align256(sizeof(half_t) * tensor_count(w->info));
 		char* const q = (char*)nnc_staging_of(ctx, ha + hb + hw);
@@ -1571,14 +1575,13 @@ static int conv_nchw_half_forw(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hin
 	Image4 as, bs;
 	dense_nhwc_f32(ai, tensor_nd(a->info.dim) == 4, A, &at, &as);
 	dense_nhwc_f32(bi, tensor_nd(b->info.dim) == 4, B, &bt, &bs);
-	if ((ret = conv_forw_nhwc(g, as, W, BI, bs, cmd.algorithm, flags, ctx)) != CCV_NNC_EXEC_SUCCESS) return ret;
+	if ((ret = conv_forw_nhwc(call, g, as, W, BI, bs, cmd.algorithm, flags, ctx)) != CCV_NNC_EXEC_SUCCESS) return ret;
 	return transpose_float_to_half(B, b->data.u8, Nb, Pb, Cb, ctx);
 }
-static int conv_nchw_half_back(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, const ccv_nnc_tensor_t* gt, const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* w, ccv_nnc_tensor_t* h, ccv_nnc_tensor_t* dw, ccv_nnc_tensor_t* dbias, ccv_nnc_stream_context_t* const ctx)
+static int conv_nchw_half_back(conv_call_t& call, const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, const conv_back_args_t& t, ccv_nnc_stream_context_t* const ctx)
 {
 	if (flags & CCV_NNC_ACCUMULATE_OUTPUT) return CCV_NNC_EXEC_NO_KERNEL;
-	const ccv_nnc_tensor_t* shape_src = a ? a : h;
-	const ccv_nnc_tensor_t* wshape = dw ? dw : w;
+	const auto [gt, a, w, h, dw, dbias, shape_src, wshape] = t;
 	if (wshape->info.format != CCV_TENSOR_FORMAT_NCHW || (w && (w->info.format != CCV_TENSOR_FORMAT_NCHW || !tensor_contiguous(w))) || (dw && !tensor_contiguous(dw))) return CCV_NNC_EXEC_NO_KERNEL;
 	int Ng, Cgr, Pg, Na, Ca, Pa;
 	if (!nchw_dense(gt, &Ng, &Cgr, &Pg) || !nchw_dense(shape_src, &Na, &Ca, &Pa) || (h && !nchw_dense(h, &Na, &Ca, &Pa))) return CCV_NNC_EXEC_NO_KERNEL;
@@ -1652,7 +1655,7 @@ static int conv_nchw_half_back(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hin
 	if (dw) {
 		if ((ret = transpose_half_to_float(a->data.u8, A, Na, Ca, Pa, ctx)) != CCV_NNC_EXEC_SUCCESS) return ret;
 		dense_nhwc_f32(ai, tensor_nd(a->info.dim) == 4, A, &as, &aim);
-		if ((ret = conv_wgrad_nhwc(g, gim, aim, DW, DB, &bias_done, cmd.algorithm, flags, ctx)) != CCV_NNC_EXEC_SUCCESS) return ret;
+		if ((ret = conv_wgrad_nhwc(call, g, gim, aim, DW, DB, &bias_done, cmd.algorithm, flags, ctx)) != CCV_NNC_EXEC_SUCCESS) return ret;
 		if ((ret = transpose_float_to_half(DW, dw->data.u8, g.K, g.kh * g.kw, g.Cg, ctx)) != CCV_NNC_EXEC_SUCCESS) return ret; // [K][khkw][C] -> [K][C][khkw]
 	}
 	if (dbias) {
@@ -1662,26 +1665,23 @@ static int conv_nchw_half_back(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hin
 	if (h) {
 		if ((ret = transpose_half_to_float(w->data.u8, W, g.K, g.Cg, g.kh * g.kw, ctx)) != CCV_NNC_EXEC_SUCCESS) return ret;
 		dense_nhwc_f32(hi, tensor_nd(h->info.dim) == 4, Hh, &hs, &him);
-		if ((ret = conv_dgrad_nhwc(g, gim, W, him, cmd.algorithm, flags, ctx)) != CCV_NNC_EXEC_SUCCESS) return ret;
+		if ((ret = conv_dgrad_nhwc(call, g, gim, W, him, cmd.algorithm, flags, ctx)) != CCV_NNC_EXEC_SUCCESS) return ret;
 		if ((ret = transpose_float_to_half(Hh, h->data.u8, Na, Pa, Ca, ctx)) != CCV_NNC_EXEC_SUCCESS) return ret;
 	}
 	return CCV_NNC_EXEC_SUCCESS;
 }
 
-static int _conv_forw_half(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
+static int _conv_forw_half(conv_call_t& call, const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
 {
-	if (input_size < 2 || output_size < 1 || !inputs[0] || !inputs[1] || !outputs[0]) return CCV_NNC_EXEC_INVALID;
-	const ccv_nnc_tensor_t* a = inputs[0];
-	const ccv_nnc_tensor_t* w = inputs[1];
-	const ccv_nnc_tensor_t* bias = input_size > 2 ? inputs[2] : 0;
-	ccv_nnc_tensor_t* b = outputs[0];
+	const auto [a, w, bias, b] = conv_forw_unpack(inputs, input_size, outputs, output_size);
+	if (!a || !w || !b) return CCV_NNC_EXEC_INVALID;
 	{
-		const int r = conv_dw_forw<half_t>(cmd, hint, flags, a, w, bias, b, stream_context);
+		const int r = conv_dw_forw<half_t>(call, cmd, hint, flags, a, w, bias, b, stream_context);
 		if (r != CCV_NNC_EXEC_NO_KERNEL) return r;
 	}
 	if (a->info.format == CCV_TENSOR_FORMAT_NCHW && b->info.format == CCV_TENSOR_FORMAT_NCHW) {
 		const int r = conv1x1_nchw_forw<half_t>(cmd, hint, flags, a, w, bias, b, stream_context);
-		return r != CCV_NNC_EXEC_NO_KERNEL ? r : conv_nchw_half_forw(cmd, hint, flags, a, w, bias, b, stream_context);
+		return r != CCV_NNC_EXEC_NO_KERNEL ? r : conv_nchw_half_forw(call, cmd, hint, flags, a, w, bias, b, stream_context);
 	}
 	if (a->info.format != CCV_TENSOR_FORMAT_NHWC || b->info.format != CCV_TENSOR_FORMAT_NHWC || w->info.format != CCV_TENSOR_FORMAT_NHWC) return CCV_NNC_EXEC_NO_KERNEL;
 	Image4 ai, bi;
@@ -1695,25 +1695,18 @@ static int _conv_forw_half(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, c
 	return conv_forw_h(g, ai, w->data.u8, bias ? bias->data.u8 : 0, bi, flags, stream_context);
 }
 
-static int _conv_back_half(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
+static int _conv_back_half(conv_call_t& call, const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
 {
-	if (input_size < 2 || output_size < 1 || !inputs[0]) return CCV_NNC_EXEC_INVALID;
-	const ccv_nnc_tensor_t* gt = inputs[0];
-	const ccv_nnc_tensor_t* a = inputs[1];
-	const ccv_nnc_tensor_t* w = input_size > 2 ? inputs[2] : 0;
-	ccv_nnc_tensor_t* h = outputs[0];
-	ccv_nnc_tensor_t* dw = output_size > 1 ? outputs[1] : 0;
-	ccv_nnc_tensor_t* dbias = output_size > 2 ? outputs[2] : 0;
-	const ccv_nnc_tensor_t* shape_src = a ? a : h;
-	const ccv_nnc_tensor_t* wshape = dw ? dw : w;
-	if (!shape_src || !wshape) return CCV_NNC_EXEC_INVALID;
+	const conv_back_args_t t = conv_back_unpack(inputs, input_size, outputs, output_size);
+	const auto [gt, a, w, h, dw, dbias, shape_src, wshape] = t;
+	if (input_size < 2 || output_size < 1 || !gt || !shape_src || !wshape) return CCV_NNC_EXEC_INVALID;
 	{
-		const int r = conv_dw_back<half_t>(cmd, hint, flags, gt, a, w, h, dw, dbias, stream_context);
+		const int r = conv_dw_back<half_t>(call, cmd, hint, flags, t, stream_context);
 		if (r != CCV_NNC_EXEC_NO_KERNEL) return r;
 	}
 	if (gt->info.format == CCV_TENSOR_FORMAT_NCHW) {
-		const int r = conv1x1_nchw_back<half_t>(cmd, hint, flags, gt, a, w, h, dw, dbias, stream_context);
-		return r != CCV_NNC_EXEC_NO_KERNEL ? r : conv_nchw_half_back(cmd, hint, flags, gt, a, w, h, dw, dbias, stream_context);
+		const int r = conv1x1_nchw_back<half_t>(cmd, hint, flags, t, stream_context);
+		return r != CCV_NNC_EXEC_NO_KERNEL ? r : conv_nchw_half_back(call, cmd, hint, flags, t, stream_context);
 	}
 	if (gt->info.format != CCV_TENSOR_FORMAT_NHWC || shape_src->info.format != CCV_TENSOR_FORMAT_NHWC || wshape->info.format != CCV_TENSOR_FORMAT_NHWC || (w && w->info.format != CCV_TENSOR_FORMAT_NHWC) || (h && h->info.format != CCV_TENSOR_FORMAT_NHWC)) return CCV_NNC_EXEC_NO_KERNEL;
 	Image4 gi, ai, hi;
@@ -1745,21 +1738,39 @@ static bool all_half(ccv_nnc_tensor_t* const* const inputs, const int input_size
 	return true;
 }
 
-// The registered exec functions: fp32 tensors -> the fp32 paths above; half precision throughout and chunk-readable -> the
-// half-precision core; any other command with a half tensor -> the fp32 paths on fp32 images.
-static int conv_forw_dispatch(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
+// The state crosses half_staged_exec as its `user` pointer, both ways: relu_done / mask_done come back from a staged run.  F = _conv_forw or _conv_back.
+template <int (*F)(conv_call_t&, const ccv_nnc_cmd_t, const ccv_nnc_hint_t, const int, ccv_nnc_tensor_t* const* const, const int, ccv_nnc_tensor_t* const* const, const int, ccv_nnc_stream_context_t* const)>
+static int conv_staged(void* const call, const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
 {
-	if (!any_half_tensor(inputs, input_size, outputs, output_size)) return _conv_forw(cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
+	return F(*(conv_call_t*)call, cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
+}
+// fp32 tensors -> the fp32 paths above; half precision throughout and chunk-readable -> the half-precision core; any other command with a half
+// tensor -> the fp32 paths on fp32 images.
+static int conv_forw_dispatch(conv_call_t& call, const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
+{
+	if (!any_half_tensor(inputs, input_size, outputs, output_size)) return _conv_forw(call, cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
 	if (all_half(inputs, input_size, outputs, output_size)) {
-		const int r = _conv_forw_half(cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
+		const int r = _conv_forw_half(call, cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
 		if (r != CCV_NNC_EXEC_NO_KERNEL) return r;
 	}
-	tl_dw_staged = 1; // (fp32 images of half or mixed tensors: the route such a command had, not the depthwise kernels on the images)
-	const int r = half_staged_exec(_conv_forw, cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
-	tl_dw_staged = 0;
-	return r;
+	call.staged = 1;
+	return half_staged_exec(conv_staged<_conv_forw>, &call, cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
 }
-static int conv_forw_entry(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context);
+static int conv_forw_entry(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
+{
+	MarkerScope marker(cmd.cmd);
+	conv_call_t call = conv_call_t();
+	// Opt-in fusion (a caller that knows the convolution's only consumer is a RELU_FORWARD): algorithm = FUSE_RELU | (0..2, or 0xff
+	// for the backend's choice).  The host's autotuner never produces such a value (it walks 0 .. algorithms - 1).
+	if (cmd.algorithm < 0 || !(cmd.algorithm & NNC_MI355X_CONV_ALGO_FUSE_RELU)) return conv_forw_dispatch(call, cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
+	if (flags & CCV_NNC_ACCUMULATE_OUTPUT) return CCV_NNC_EXEC_INVALID;
+	ccv_nnc_cmd_t plain = cmd;
+	plain.algorithm = (cmd.algorithm & 0xff) == 0xff ? -1 : (cmd.algorithm & 0xff);
+	call.relu_want = 1;
+	const int r = conv_forw_dispatch(call, plain, hint, flags, inputs, input_size, outputs, output_size, stream_context);
+	if (r != CCV_NNC_EXEC_SUCCESS || call.relu_done) return r;
+	return relu_inplace(outputs[0], stream_context); // the path taken has no fused epilogue (implicit GEMM, half core, ...): one more pass
+}
 // The registered entry: a convolution whose like has run before is recorded, not launched -- the in-place RELU_FORWARD the reference's
 // graphs issue next folds into it (peephole.cpp); anything else on the stream launches it as it is.
 static int _conv_forw_any(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
@@ -1771,34 +1782,16 @@ static int _conv_forw_any(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, co
 	if (r == CCV_NNC_EXEC_SUCCESS) deferred_mark_good(sig);
 	return r;
 }
-static int conv_forw_entry(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
+
+static int conv_back_dispatch(conv_call_t& call, const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
 {
-	MarkerScope marker(cmd.cmd);
-	// Opt-in fusion (a caller that knows the convolution's only consumer is a RELU_FORWARD): algorithm = FUSE_RELU | (0..2, or 0xff
-	// for the backend's choice).  The host's autotuner never produces such a value (it walks 0 .. algorithms - 1).
-	if (cmd.algorithm < 0 || !(cmd.algorithm & NNC_MI355X_CONV_ALGO_FUSE_RELU)) return conv_forw_dispatch(cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
-	if (flags & CCV_NNC_ACCUMULATE_OUTPUT) return CCV_NNC_EXEC_INVALID;
-	ccv_nnc_cmd_t plain = cmd;
-	plain.algorithm = (cmd.algorithm & 0xff) == 0xff ? -1 : (cmd.algorithm & 0xff);
-	tl_relu_want = 1; tl_relu_done = 0;
-	const int r = conv_forw_dispatch(plain, hint, flags, inputs, input_size, outputs, output_size, stream_context);
-	const int done = tl_relu_done;
-	tl_relu_want = 0; tl_relu_done = 0;
-	if (r != CCV_NNC_EXEC_SUCCESS || done) return r;
-	return relu_inplace(outputs[0], stream_context); // the path taken has no fused epilogue (implicit GEMM, half core, ...): one more pass
-}
-static int conv_back_dispatch(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context);
-// NNC_MI355X_CONV_ALGO_FUSE_RELU on the backward command: h = a > 0 ? (data gradient) : 0 -- the RELU_BACKWARD of the map a that would
-// run on h next.  Masked where the data gradient is written by the Winograd kernels; one in-place pass behind the others.
-static int conv_back_entry(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context);
-static int _conv_back_any(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
-{
-	uint64_t sig; // (recorded like the forward: the RELU_BACKWARD of the map this command read may follow on the gradient it writes)
-	if (const int e = deferred_take_error(stream_context)) return e; // a recorded command failed when a flush launched it (peephole.cpp)
-	if (deferred_try(_conv_back_any, DEFER_CONV_BACKWARD, cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context, &sig)) return CCV_NNC_EXEC_SUCCESS;
-	const int r = conv_back_entry(cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
-	if (r == CCV_NNC_EXEC_SUCCESS) deferred_mark_good(sig);
-	return r;
+	if (!any_half_tensor(inputs, input_size, outputs, output_size)) return _conv_back(call, cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
+	if (all_half(inputs, input_size, outputs, output_size)) {
+		const int r = _conv_back_half(call, cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
+		if (r != CCV_NNC_EXEC_NO_KERNEL) return r;
+	}
+	call.staged = 1;
+	return half_staged_exec(conv_staged<_conv_back>, &call, cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
 }
 // the weight / bias gradients of a backward command that has just been enqueued: the overlapped all-reduce of deployment (b) starts behind THEM, not behind
 // the rest of the backward pass (cmd_comm.cpp "Overlap"); an accumulating command is one of several writers: stream order for that gradient
@@ -1811,33 +1804,31 @@ static int conv_back_report(const int r, const int flags, ccv_nnc_tensor_t* cons
 	}
 	return r;
 }
+// NNC_MI355X_CONV_ALGO_FUSE_RELU on the backward command: h = a > 0 ? (data gradient) : 0 -- the RELU_BACKWARD of the map a that would
+// run on h next.  Masked where the data gradient is written by the Winograd kernels; one in-place pass behind the others.
 static int conv_back_entry(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
 {
 	MarkerScope marker(cmd.cmd);
-	if (cmd.algorithm < 0 || !(cmd.algorithm & NNC_MI355X_CONV_ALGO_FUSE_RELU)) return conv_back_report(conv_back_dispatch(cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context), flags, outputs, output_size, stream_context);
+	conv_call_t call = conv_call_t();
+	if (cmd.algorithm < 0 || !(cmd.algorithm & NNC_MI355X_CONV_ALGO_FUSE_RELU)) return conv_back_report(conv_back_dispatch(call, cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context), flags, outputs, output_size, stream_context);
 	ccv_nnc_cmd_t plain = cmd;
 	plain.algorithm = (cmd.algorithm & 0xff) == 0xff ? -1 : (cmd.algorithm & 0xff);
 	ccv_nnc_tensor_t* const h = output_size > 0 ? outputs[0] : 0;
 	const ccv_nnc_tensor_t* const a = input_size > 1 ? inputs[1] : 0;
-	if (!h) return conv_back_report(conv_back_dispatch(plain, hint, flags, inputs, input_size, outputs, output_size, stream_context), flags, outputs, output_size, stream_context); // no data gradient asked for: nothing to mask
+	if (!h) return conv_back_report(conv_back_dispatch(call, plain, hint, flags, inputs, input_size, outputs, output_size, stream_context), flags, outputs, output_size, stream_context); // no data gradient asked for: nothing to mask
 	if ((flags & CCV_NNC_ACCUMULATE_OUTPUT) || !a || !tensor_contiguous(h) || !tensor_contiguous(a) || h->info.datatype != a->info.datatype || h->info.format != a->info.format || tensor_count(h->info) != tensor_count(a->info)) return CCV_NNC_EXEC_INVALID;
-	tl_mask_want = 1; tl_mask_done = 0;
-	const int r = conv_back_report(conv_back_dispatch(plain, hint, flags, inputs, input_size, outputs, output_size, stream_context), flags, outputs, output_size, stream_context);
-	const int done = tl_mask_done;
-	tl_mask_want = 0; tl_mask_done = 0; tl_mask.p = 0;
-	if (r != CCV_NNC_EXEC_SUCCESS || done) return r;
+	call.mask_want = 1;
+	const int r = conv_back_report(conv_back_dispatch(call, plain, hint, flags, inputs, input_size, outputs, output_size, stream_context), flags, outputs, output_size, stream_context);
+	if (r != CCV_NNC_EXEC_SUCCESS || call.mask_done) return r;
 	return relu_back_inplace(h, a, stream_context);
 }
-static int conv_back_dispatch(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
+static int _conv_back_any(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
 {
-	if (!any_half_tensor(inputs, input_size, outputs, output_size)) return _conv_back(cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
-	if (all_half(inputs, input_size, outputs, output_size)) {
-		const int r = _conv_back_half(cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
-		if (r != CCV_NNC_EXEC_NO_KERNEL) return r;
-	}
-	tl_dw_staged = 1;
-	const int r = half_staged_exec(_conv_back, cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
-	tl_dw_staged = 0;
+	uint64_t sig; // (recorded like the forward: the RELU_BACKWARD of the map this command read may follow on the gradient it writes)
+	if (const int e = deferred_take_error(stream_context)) return e; // a recorded command failed when a flush launched it (peephole.cpp)
+	if (deferred_try(_conv_back_any, DEFER_CONV_BACKWARD, cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context, &sig)) return CCV_NNC_EXEC_SUCCESS;
+	const int r = conv_back_entry(cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
+	if (r == CCV_NNC_EXEC_SUCCESS) deferred_mark_good(sig);
 	return r;
 }
 
@@ -1872,7 +1863,8 @@ static int _conv_autotune(const ccv_nnc_cmd_t cmd, const size_t max_workspace_si
 		int ok = 1;
 		for (int trial = 0; trial < 2 && ok; trial++) { // first trial warms the workspace up
 			HIP_ENFORCE(hipEventRecord(e0, stream));
-			const int ret = fwd ? _conv_forw(c, hint, trial_flags, inputs, input_size, outputs, output_size, stream_context) : _conv_back(c, hint, trial_flags, inputs, input_size, outputs, output_size, stream_context);
+			conv_call_t call = conv_call_t();
+			const int ret = fwd ? _conv_forw(call, c, hint, trial_flags, inputs, input_size, outputs, output_size, stream_context) : _conv_back(call, c, hint, trial_flags, inputs, input_size, outputs, output_size, stream_context);
 			HIP_ENFORCE(hipEventRecord(e1, stream));
 			HIP_ENFORCE(hipEventSynchronize(e1));
 			if (ret != CCV_NNC_EXEC_SUCCESS) ok = 0;

@@ -292,11 +292,14 @@ __device__ __forceinline__ float fold_phases(float (*red)[FOLD_CH], const int ch
 // staging arena.  NNC_HALF_STAGED(registry, EXEC) -- used by every row's registration -- adds CCV_16F next to CCV_32F and routes
 // the row through the wrapper (which is a plain call of EXEC when no tensor is half precision).
 typedef int (*nnc_exec_f)(const ccv_nnc_cmd_t, const ccv_nnc_hint_t, const int, ccv_nnc_tensor_t* const* const, const int, ccv_nnc_tensor_t* const* const, const int, ccv_nnc_stream_context_t* const);
+// (the form with `user`: a row's own state for the command, handed to `inner` as it is -- cmd_conv.cpp's conv_call_t; the other two are plain calls of it)
+typedef int (*nnc_exec_user_f)(void* user, const ccv_nnc_cmd_t, const ccv_nnc_hint_t, const int, ccv_nnc_tensor_t* const* const, const int, ccv_nnc_tensor_t* const* const, const int, ccv_nnc_stream_context_t* const);
+int half_staged_exec(nnc_exec_user_f inner, void* user, const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const ctx);
 int half_staged_exec(nnc_exec_f inner, const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const ctx);
 template <nnc_exec_f F>
 static int half_staged(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const ctx)
 {
-	return half_staged_exec(F, cmd, hint, flags, inputs, input_size, outputs, output_size, ctx);
+	return half_staged_exec([](void*, const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const ctx) { return F(cmd, hint, flags, inputs, input_size, outputs, output_size, ctx); }, 0, cmd, hint, flags, inputs, input_size, outputs, output_size, ctx);
 }
 #define NNC_HALF_STAGED(registry, EXEC) do { if (((registry)->tensor_datatypes & CCV_32F) && !((registry)->tensor_datatypes & CCV_16F)) { /* rows that list CCV_16F themselves handle it natively */ (registry)->tensor_datatypes |= CCV_16F; (registry)->exec = nnc::half_staged<EXEC>; } } while (0)
 bool any_half_tensor(ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size);

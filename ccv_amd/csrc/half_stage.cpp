@@ -316,11 +316,11 @@ static const native_half_t* native_half_row(const uint32_t cmd, const int flags,
 	return 0;
 }
 
-int half_staged_exec(const nnc_exec_f inner, const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const ctx)
+int half_staged_exec(const nnc_exec_user_f inner, void* const user, const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const ctx)
 {
 	MarkerScope marker(cmd.cmd); // every row registered through NNC_HALF_STAGED passes here: the per-command roctx range
 	if (!any_half_tensor(inputs, input_size, outputs, output_size)) {
-		const int r = inner(cmd, hint, flags, inputs, input_size, outputs, output_size, ctx);
+		const int r = inner(user, cmd, hint, flags, inputs, input_size, outputs, output_size, ctx);
 		warn_refused(cmd.cmd, r);
 		return r;
 	}
@@ -395,7 +395,7 @@ int half_staged_exec(const nnc_exec_f inner, const ccv_nnc_cmd_t cmd, const ccv_
 	// (peephole.cpp) would record a batch norm / convolution here; a recorded command launched by a flush has no caller to report a failure to, and this
 	// function went on to convert the never-written image down to half and return SUCCESS.  So: no recording underneath.
 	if (nst) deferred_suppress(1);
-	const int ret = inner(cmd, hint, flags, in_s, input_size, out_s, output_size, ctx);
+	const int ret = inner(user, cmd, hint, flags, in_s, input_size, out_s, output_size, ctx);
 	if (nst) deferred_suppress(-1);
 	warn_refused(cmd.cmd, ret);
 	if (ret != CCV_NNC_EXEC_SUCCESS) return ret;
@@ -410,6 +410,10 @@ int half_staged_exec(const nnc_exec_f inner, const ccv_nnc_cmd_t cmd, const ccv_
 		else float_to_half(st[e].image, st[e].half, tensor_count(outputs[i]->info), ctx);
 	}
 	return CCV_NNC_EXEC_SUCCESS;
+}
+int half_staged_exec(const nnc_exec_f inner, const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const ctx)
+{
+	return half_staged_exec([](void* const f, const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const ctx) { return ((nnc_exec_f)f)(cmd, hint, flags, inputs, input_size, outputs, output_size, ctx); }, (void*)inner, cmd, hint, flags, inputs, input_size, outputs, output_size, ctx);
 }
 
 } // namespace nnc
