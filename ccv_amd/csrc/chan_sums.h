@@ -1,0 +1,149 @@
+// Column and channel sums: out[c] (+)= the sum of everything in column / channel c.  Every bias gradient (GEMM, convolution, LSTM), the layer-norm and
+// RMS-norm parameter gradients and the batch-norm statistics end here.
+//
+// One scheme throughout, two deterministic stages: per-slice (per-plane) fp32 partials go to the BASE of the stream workspace, a 16 x 16 fold
+// (common.h: fold_slices / fold_phases) adds them in a fixed order.  What lives here:
+//   * the slice plan of the row forms (colsum_plan) and, next to it, what each form asks of the workspace -- a caller that keeps data of its own
+//     behind the partials takes its head size from these functions, never from a restatement of the plan;
+//   * the kernel templates: rows (lanes = 64 consecutive columns), planes (a wave per plane), the fold (fp32 or half output, an optional second array);
+//   * chan_reduce, the launcher over a [outer][C][inner] view with the batch-norm functors (cmd_norm.cpp uses it with all three);
+//   * chan_sums.cpp: the 16-byte float rows kernel, the grouped level for thousands of slices, and the five exported sums declared in common.h.
+// The route decides the order of the additions and so the bits: see each launcher for which kernel it takes when.
+#pragma once
+#include "common.h"
+
+namespace nnc {
+
+typedef _Float16 half_t;
+
+// ---- the plan and the workspace each form takes ------------------------------------------------------------------------------------------------------
+// rows x cols, columns contiguous: 64-column tiles x row slices, about four workgroups per CU, no slice under 64 rows, none empty.
+struct colsum_plan_t { int col_tiles; long slices, rows_per_slice; };
+colsum_plan_t colsum_plan(long rows, int cols);
+size_t colsum_workspace_bytes(long rows, int cols); // what colsum_f32 / colsum_f16 / chan_reduce (inner == 1) request for this shape
+size_t colsum_workspace_bound(int cols); // the most they request for `cols` columns, whatever the rows
+size_t colsum_partials_bytes(long slices, int cols); // what colsum_partials_f16's caller provides: its partials and room for the grouped level behind them
+inline size_t chan_planes_workspace_bytes(const long outer, const int C) { return sizeof(float) * (size_t)outer * (size_t)C; } // inner > 1: one partial per plane
+
+// ---- which reduction: the value element (x, g) of channel c contributes ---------------------------------------------------------------------------------
+struct chan_view_t { long outer; int C; long inner; };
+struct RSum { __device__ float operator()(float x, float, int) const { return x; } };
+struct RCenteredSq { const float* mean; __device__ float operator()(float x, float, int c) const { const float w = x - mean[c]; return w * w; } };
+struct RXhatG { const float* mean; const float* inv_std; __device__ float operator()(float x, float g, int c) const { return (x - mean[c]) * inv_std[c] * g; } };
+
+// ---- kernels ---------------------------------------------------------------------------------------------------------------------------------------------
+constexpr int RC_COLS = 64, RC_PHASES = 4;
+// rows of C contiguous channels, `ld` elements apart.  grid (ceil(C / 64), slices); each wave owns one row phase, lanes = 64 consecutive channels.
+template <class F, bool USE_G, class T>
+__global__ void __launch_bounds__(256) chan_reduce_rows_kernel(F f, const T* x, const T* g, const long rows, const int C, const long ld, const long rows_per_slice, float* partial)
+{
+	__shared__ float red[RC_PHASES][RC_COLS];
+	const int lane = threadIdx.x & 63, phase = threadIdx.x >> 6;
+	const int c = blockIdx.x * RC_COLS + lane;
+	const long r0 = (long)blockIdx.y * rows_per_slice;
+	long r1 = r0 + rows_per_slice;
+	if (r1 > rows) r1 = rows;
+	float s = 0.f;
+	if (c < C)
+		for (long r = r0 + phase; r < r1; r += RC_PHASES) s += f((float)x[r * ld + c], USE_G ? (float)g[r * ld + c] : 0.f, c);
+	red[phase][lane] = s;
+	__syncthreads();
+	if (phase == 0 && c < C) partial[(long)blockIdx.y * C + c] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+}
+// planes of `inner` contiguous elements, ONE WAVE PER PLANE (16-byte lanes when the plane allows: a workgroup per plane left 7 x 7 planes with 49 busy threads), partial[o][c].
+template <class T> struct pack16 { typedef T type __attribute__((ext_vector_type(16 / sizeof(T)))); }; // one 16-byte access: 4 floats / 8 halves
+template <class F, bool USE_G, class T>
+__global__ void __launch_bounds__(256) chan_reduce_planes_kernel(F f, const T* x, const T* g, const int C, const long inner, const long planes, float* partial)
+{
+	constexpr int W = 16 / sizeof(T);
+	typedef typename pack16<T>::type V;
+	const int lane = threadIdx.x & 63;
+	const long nw = (long)gridDim.x * 4;
+	for (long pl = (long)blockIdx.x * 4 + (threadIdx.x >> 6); pl < planes; pl += nw) {
+		const int c = (int)(pl % C);
+		const T* const xp = x + pl * inner;
+		const T* const gp = USE_G ? g + pl * inner : x;
+		float s = 0.f;
+		if ((inner % W) == 0 && ((((uintptr_t)xp) | ((uintptr_t)gp)) & 15) == 0) {
+			const long nv = inner / W;
+			for (long i = lane; i < nv; i += 64) {
+				const V xv = ((const V*)xp)[i];
+				V gv = xv;
+				if (USE_G) gv = ((const V*)gp)[i];
+#pragma unroll
+				for (int e = 0; e < W; e++) s += f((float)xv[e], USE_G ? (float)gv[e] : 0.f, c);
+			}
+		} else
+			for (long i = lane; i < inner; i += 64) s += f((float)xp[i], USE_G ? (float)gp[i] : 0.f, c);
+		for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+		if (lane == 0) partial[pl] = s;
+	}
+}
+// Folding per-slice (per-plane) partials into per-channel sums, fixed order, 16 channels x 16 phases per workgroup (common.h).
+// out0[c] (+)= sum_i p0[i][c]  and, when p1 is given, out1[c] (+)= sum_i p1[i][c]  (blockIdx.y picks the array); halves are rounded once, at the end.
+template <class TO>
+__global__ void __launch_bounds__(256) chan_fold_kernel(const float* p0, const float* p1, const long slices, const int C, TO* out0, TO* out1, const int accumulate)
+{
+	__shared__ float red[FOLD_PH][FOLD_CH];
+	const int ch = threadIdx.x & (FOLD_CH - 1), phase = threadIdx.x / FOLD_CH;
+	const int c = blockIdx.x * FOLD_CH + ch;
+	const float* const p = blockIdx.y ? p1 : p0;
+	TO* const out = blockIdx.y ? out1 : out0;
+	red[phase][ch] = c < C ? fold_slices(p, slices, C, c, phase) : 0.f;
+	__syncthreads();
+	if (phase == 0 && c < C) {
+		const float v = fold_phases(red, ch);
+		out[c] = (TO)(accumulate ? (float)out[c] + v : v);
+	}
+}
+
+// ---- launchers -------------------------------------------------------------------------------------------------------------------------------------------
+// one plane per wave over the WHOLE tensor, no grid-stride cap (round 3): the same lesson as the element-wise maps (section 3.2 of DESIGN.md -- a few
+// thousand workgroups striding a multi-GB tensor keep DRAM pages from all over it in flight, a front of workgroups walking it in order does not; the
+// capped form ran the batch-norm passes at ~3.4 TB/s).  TUNE_GRID_WG_PER_CU > 0 restores a cap.
+static inline unsigned plane_grid(const long planes)
+{
+	const long want = (planes + 3) / 4, per_cu = tune(TUNE_GRID_WG_PER_CU);
+	const long cap = per_cu > 0 ? (long)device_cu_count() * per_cu : 0x7fffffffL;
+	return (unsigned)(want < cap ? (want > 0 ? want : 1) : cap);
+}
+template <class TO>
+static int chan_fold(const float* partial, const long slices, const int C, TO* out, const int accumulate, hipStream_t stream)
+{
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(chan_fold_kernel<TO>), dim3((C + FOLD_CH - 1) / FOLD_CH), dim3(256), 0, stream, partial, (const float*)0, slices, C, out, (TO*)0, accumulate);
+	HIP_ENFORCE(hipGetLastError());
+	return CCV_NNC_EXEC_SUCCESS;
+}
+// out[c] (+)= sum_r f(x[r * ld + c], g[r * ld + c], c): always the scalar rows kernel (chan_sums.cpp's colsum_f32 alone picks the 16-byte one where it can)
+template <class F, bool USE_G, class T, class TO>
+static int chan_reduce_rows(F f, const T* x, const T* g, const long rows, const int C, const long ld, TO* out, const int accumulate, ccv_nnc_stream_context_t* ctx)
+{
+	const colsum_plan_t p = colsum_plan(rows, C);
+	float* const partial = (float*)workspace_of(ctx, colsum_workspace_bytes(rows, C));
+	if (!partial) return CCV_NNC_EXEC_OOM;
+	hipStream_t stream = stream_of(ctx);
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(chan_reduce_rows_kernel<F, USE_G, T>), dim3(p.col_tiles, (unsigned)p.slices), dim3(256), 0, stream, f, x, g, rows, C, ld, p.rows_per_slice, partial);
+	HIP_ENFORCE(hipGetLastError());
+	return chan_fold(partial, p.slices, C, out, accumulate, stream);
+}
+// out[c] (+)= sum over (o, i) of f(.) at [(o * C + c) * inner + i]
+template <class F, bool USE_G, class T, class TO>
+static int chan_reduce_planes(F f, const T* x, const T* g, const chan_view_t& v, TO* out, const int accumulate, ccv_nnc_stream_context_t* ctx)
+{
+	float* const partial = (float*)workspace_of(ctx, chan_planes_workspace_bytes(v.outer, v.C));
+	if (!partial) return CCV_NNC_EXEC_OOM;
+	hipStream_t stream = stream_of(ctx);
+	const long planes = v.outer * v.C;
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(chan_reduce_planes_kernel<F, USE_G, T>), dim3(plane_grid(planes)), dim3(256), 0, stream, f, x, g, v.C, v.inner, planes, partial);
+	HIP_ENFORCE(hipGetLastError());
+	return chan_fold(partial, v.outer, v.C, out, accumulate, stream);
+}
+// NHWC-style views (inner == 1) are rows of C channels, everything else planes
+template <class F, bool USE_G, class T = float>
+static int chan_reduce(F f, const T* x, const T* g, const chan_view_t& v, float* out, ccv_nnc_stream_context_t* ctx, const int accumulate = 0)
+{
+	if (v.inner == 1) return chan_reduce_rows<F, USE_G, T>(f, x, g, v.outer, v.C, v.C, out, accumulate, ctx);
+	return chan_reduce_planes<F, USE_G, T>(f, x, g, v, out, accumulate, ctx);
+}
+
+} // namespace nnc

@@ -7,6 +7,7 @@
 // Layout on device: NHWC activations (n, y, x, c) with c innermost, weights [K][kh][kw][Cg]; tensor views are accepted for
 // the inputs as long as the channel stride is 1.  NCHW tensors are routed through the layout kernels of cmd_util (workspace).
 #include "gemm_launch.h"
+#include "chan_sums.h"
 #include "winograd.h"
 #include "wino_fused.h"
 #include "wino_wgrad_fused.h"
@@ -353,8 +354,7 @@ static bool wino_wgrad_plan(const conv_geom_t& g, wino_wgrad_plan_t* p)
 	p->du_bytes = (sizeof(float) * 36 * (size_t)g.K * g.C + 255) & ~(size_t)255;
 	// head: what the calls made underneath take from the base of the workspace -- gemm_run's slab sets, colsum_f32's partials
 	p->head_bytes = p->splits > 1 ? sizeof(float) * 36 * (size_t)g.K * g.C * p->splits : 0;
-	const size_t colsum_bound = sizeof(float) * (size_t)device_cu_count() * 4 * g.K;
-	if (p->head_bytes < colsum_bound) p->head_bytes = colsum_bound;
+	if (p->head_bytes < colsum_workspace_bound(g.K)) p->head_bytes = colsum_workspace_bound(g.K);
 	p->head_bytes = (p->head_bytes + 255) & ~(size_t)255;
 	p->blocks = ((long)p->t.T * (g.K / 4) + 255) / 256;
 	p->bp_bytes = sizeof(float) * (size_t)p->blocks * g.K;
@@ -1610,7 +1610,7 @@ static int conv_nchw_half_back(conv_call_t& call, const ccv_nnc_cmd_t cmd, const
 		bool bias_done = false;
 		if (dbias) {
 			const long slices = transpose_half_rowsum_slices(Ng, Pg);
-			float* const part = (float*)workspace_of(ctx, sizeof(float) * (size_t)(slices + 256) * (size_t)Cgr); // (+ 256 rows: colsum_partials_f16's grouped level)
+			float* const part = (float*)workspace_of(ctx, colsum_partials_bytes(slices, Cgr));
 			if (part && transpose_half_rowsum(gt->data.u8, G16, Ng, Cgr, Pg, part, ctx) == CCV_NNC_EXEC_SUCCESS) {
 				if ((ret = colsum_partials_f16(part, slices, g.K, dbias->data.u8, 0, ctx)) != CCV_NNC_EXEC_SUCCESS) return ret;
 				bias_done = true;

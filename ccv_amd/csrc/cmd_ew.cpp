@@ -1,5 +1,4 @@
-// Bandwidth-bound element-wise commands on gfx950: RELU, EWSUM, SCALAR_MUL, SGD, SET, DATA_TRANSFER, plus the
-// column-sum used for bias gradients.  16 bytes per lane where the tensors allow it; the element-wise map is a tile per workgroup over a full grid, the others grid-stride
+// Bandwidth-bound element-wise commands on gfx950: RELU, EWSUM, SCALAR_MUL, SGD, SET, DATA_TRANSFER.  16 bytes per lane where the tensors allow it; the element-wise map is a tile per workgroup over a full grid, the others grid-stride
 // (coalesced dwordx4), otherwise 4 bytes per lane.  Roofline for every kernel here is HBM (8 TB/s spec);
 // algorithmic bytes are listed per kernel.
 // Oracle semantics:
@@ -196,61 +195,6 @@ __global__ void __launch_bounds__(EW_THREADS) sgd_multi_kernel(const sgd_multi_t
 	}
 	((V*)s.nm[k])[i] = no;
 	((V*)s.b[k])[i] = bo;
-}
-
-// ---- column sum: out[c] (+)= sum_r x[r*ld + c].  Stage 1: grid (col tiles of 64, row slices); each wave owns one
-// row phase, lanes = 64 consecutive columns (256-byte coalesced rows); stage 2 folds the slices in fixed order. ------
-constexpr int CS_COLS = 64, CS_PHASES = 4;
-__global__ void __launch_bounds__(256) colsum_partial_kernel(const float* x, const long rows, const int cols, const long ld, const long rows_per_slice, float* partial)
-{
-	__shared__ float red[CS_PHASES][CS_COLS];
-	const int lane = threadIdx.x & 63, phase = threadIdx.x >> 6;
-	const int c = blockIdx.x * CS_COLS + lane;
-	const long r0 = (long)blockIdx.y * rows_per_slice;
-	long r1 = r0 + rows_per_slice;
-	if (r1 > rows) r1 = rows;
-	float s = 0.f;
-	if (c < cols)
-		for (long r = r0 + phase; r < r1; r += CS_PHASES) s += x[r * ld + c];
-	red[phase][lane] = s;
-	__syncthreads();
-	if (phase == 0 && c < cols) partial[(long)blockIdx.y * cols + c] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
-}
-// 16-byte variant (cols % 4 == 0, ld % 4 == 0, 16-byte aligned): 16 lanes x float4 cover the 64 columns of a tile, the
-// other 16 lane groups of the block walk 16 row phases; fixed-order fold of the phases through LDS.
-__global__ void __launch_bounds__(256) colsum_partial_v4_kernel(const float* x, const long rows, const int cols, const long ld, const long rows_per_slice, float* partial)
-{
-	__shared__ float4 red[16][16];
-	const int q = threadIdx.x & 15, phase = threadIdx.x >> 4;
-	const int c = blockIdx.x * CS_COLS + q * 4;
-	const long r0 = (long)blockIdx.y * rows_per_slice;
-	long r1 = r0 + rows_per_slice;
-	if (r1 > rows) r1 = rows;
-	float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-	if (c < cols)
-		for (long r = r0 + phase; r < r1; r += 16) {
-			const float4 v = *(const float4*)(x + r * ld + c);
-			s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-		}
-	red[phase][q] = s;
-	__syncthreads();
-	if (phase == 0 && c < cols) {
-		float4 t = red[0][q];
-		for (int p = 1; p < 16; p++) { const float4 u = red[p][q]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
-		*(float4*)(partial + (long)blockIdx.y * cols + c) = t;
-	}
-}
-__global__ void __launch_bounds__(256) colsum_final_kernel(const float* partial, const int slices, const int cols, float* out, const int accumulate)
-{ // 16 columns x 16 phases per workgroup (common.h: fold_slices / fold_phases)
-	__shared__ float red[FOLD_PH][FOLD_CH];
-	const int ch = threadIdx.x & (FOLD_CH - 1), phase = threadIdx.x / FOLD_CH;
-	const int c = blockIdx.x * FOLD_CH + ch;
-	red[phase][ch] = c < cols ? fold_slices(partial, slices, cols, c, phase) : 0.f;
-	__syncthreads();
-	if (phase == 0 && c < cols) {
-		const float s = fold_phases(red, ch);
-		out[c] = accumulate ? out[c] + s : s;
-	}
 }
 
 static int _relu_forw(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
@@ -741,29 +685,6 @@ int relu_back_inplace(ccv_nnc_tensor_t* h, const ccv_nnc_tensor_t* b, ccv_nnc_st
 	const int dt = CCV_GET_DATA_TYPE(h->info.datatype);
 	if (dt != CCV_32F && dt != CCV_16F) return CCV_NNC_EXEC_INVALID;
 	return ew_map_any<OpReluBack, 2>(OpReluBack(), h->info.datatype, h->data.u8, h->data.u8, b->data.u8, 0, tensor_count(h->info), ctx);
-}
-
-int colsum_f32(const float* x, long rows, int cols, long ld, float* out, int accumulate, ccv_nnc_stream_context_t* ctx)
-{
-	if (cols <= 0) return CCV_NNC_EXEC_SUCCESS;
-	hipStream_t stream = stream_of(ctx);
-	const int col_tiles = (cols + CS_COLS - 1) / CS_COLS;
-	long slices = ((long)device_cu_count() * 4 + col_tiles - 1) / col_tiles;
-	const long max_slices = (rows + 63) / 64;
-	if (slices > max_slices) slices = max_slices;
-	if (slices < 1) slices = 1;
-	const long rows_per_slice = (rows + slices - 1) / slices;
-	slices = rows > 0 ? (rows + rows_per_slice - 1) / rows_per_slice : 1;
-	float* partial = (float*)workspace_of(ctx, sizeof(float) * (size_t)slices * cols);
-	if (!partial) return CCV_NNC_EXEC_OOM;
-	if (cols % 4 == 0 && ld % 4 == 0 && aligned16(x) && aligned16(partial))
-		hipLaunchKernelGGL(colsum_partial_v4_kernel, dim3(col_tiles, (unsigned)slices), dim3(256), 0, stream, x, rows, cols, ld, rows_per_slice > 0 ? rows_per_slice : 1, partial);
-	else
-		hipLaunchKernelGGL(colsum_partial_kernel, dim3(col_tiles, (unsigned)slices), dim3(256), 0, stream, x, rows, cols, ld, rows_per_slice > 0 ? rows_per_slice : 1, partial);
-	HIP_ENFORCE(hipGetLastError());
-	hipLaunchKernelGGL(colsum_final_kernel, dim3((cols + FOLD_CH - 1) / FOLD_CH), dim3(256), 0, stream, (const float*)partial, (int)slices, cols, out, accumulate);
-	HIP_ENFORCE(hipGetLastError());
-	return CCV_NNC_EXEC_SUCCESS;
 }
 
 } // namespace nnc

@@ -19,6 +19,7 @@
 // planes of B x H -- i, f, g, o, tanh(c), [projected h], [dropout scale] --, then the cell state after each of the first T - 1 steps.
 #include <optional>
 #include "gemm_launch.h"
+#include "chan_sums.h"
 #include "isa.h"
 
 using namespace nnc;
@@ -726,7 +727,7 @@ static size_t lstm_inner_bytes(const lstm_geom_t& g)
 { // what the contractions and the column sum made underneath may ask of the workspace (split-K slabs: the bound is not monotonic in the shape, so every shape is listed)
 	const long TB = (long)g.T * g.B, G4 = 4L * g.H;
 	const int ins[2] = { g.I, g.D * g.P };
-	size_t inner = sizeof(float) * ((size_t)device_cu_count() * 4 + 64) * 4 * g.H; // colsum_f32's partials
+	size_t inner = colsum_workspace_bound(4 * g.H); // colsum_f32's partials
 	auto take = [&](const long M, const long N, const long K) { const size_t v = gemm_workspace_bound(M, N, K); if (v > inner) inner = v; };
 	for (int i = 0; i < 2; i++) {
 		take(TB, G4, ins[i]); // gx = X W^T

@@ -7,120 +7,13 @@
 //
 // x is viewed as [outer][C][inner] around the one axis the statistics keep (NHWC: inner = 1, outer = N*H*W; NCHW:
 // outer = N, inner = H*W).  Per-channel reductions run in two deterministic stages (slice partials in the stream
-// workspace, fixed-order fold), wavefront-coalesced in whichever of C / inner is contiguous.
-#include "common.h"
+// workspace, fixed-order fold), wavefront-coalesced in whichever of C / inner is contiguous: chan_reduce and the fold kernel of chan_sums.h.
+#include "chan_sums.h"
 #include "isa.h"
 
 using namespace nnc;
 
 namespace {
-
-struct chan_view_t { long outer; int C; long inner; };
-
-// which reduction: value contributed by element (x, g) of channel c
-struct RSum { __device__ float operator()(float x, float, int) const { return x; } };
-struct RCenteredSq { const float* mean; __device__ float operator()(float x, float, int c) const { const float w = x - mean[c]; return w * w; } };
-struct RXhatG { const float* mean; const float* inv_std; __device__ float operator()(float x, float g, int c) const { return (x - mean[c]) * inv_std[c] * g; } };
-
-constexpr int RC_COLS = 64, RC_PHASES = 4;
-// inner == 1: rows of C contiguous channels.  grid (ceil(C/64), slices); lanes = 64 consecutive channels.
-static unsigned plane_grid(const long planes);
-template <class F, bool USE_G, class T>
-__global__ void __launch_bounds__(256) chan_reduce_rows_kernel(F f, const T* x, const T* g, const long rows, const int C, const long rows_per_slice, float* partial)
-{
-	__shared__ float red[RC_PHASES][RC_COLS];
-	const int lane = threadIdx.x & 63, phase = threadIdx.x >> 6;
-	const int c = blockIdx.x * RC_COLS + lane;
-	const long r0 = (long)blockIdx.y * rows_per_slice;
-	long r1 = r0 + rows_per_slice;
-	if (r1 > rows) r1 = rows;
-	float s = 0.f;
-	if (c < C)
-		for (long r = r0 + phase; r < r1; r += RC_PHASES) s += f((float)x[r * C + c], USE_G ? (float)g[r * C + c] : 0.f, c);
-	red[phase][lane] = s;
-	__syncthreads();
-	if (phase == 0 && c < C) partial[(long)blockIdx.y * C + c] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
-}
-// inner > 1: planes of `inner` contiguous elements, ONE WAVE PER PLANE (16-byte lanes when the plane allows), partial[o][c].
-typedef _Float16 half_t;
-template <class T> struct pack16 { typedef T type __attribute__((ext_vector_type(16 / sizeof(T)))); }; // one 16-byte access: 4 floats / 8 halves
-template <class F, bool USE_G, class T>
-__global__ void __launch_bounds__(256) chan_reduce_planes_kernel(F f, const T* x, const T* g, const int C, const long inner, const long planes, float* partial)
-{
-	constexpr int W = 16 / sizeof(T);
-	typedef typename pack16<T>::type V;
-	const int lane = threadIdx.x & 63;
-	const long nw = (long)gridDim.x * 4;
-	for (long pl = (long)blockIdx.x * 4 + (threadIdx.x >> 6); pl < planes; pl += nw) {
-		const int c = (int)(pl % C);
-		const T* const xp = x + pl * inner;
-		const T* const gp = USE_G ? g + pl * inner : x;
-		float s = 0.f;
-		if ((inner % W) == 0 && ((((uintptr_t)xp) | ((uintptr_t)gp)) & 15) == 0) {
-			const long nv = inner / W;
-			for (long i = lane; i < nv; i += 64) {
-				const V xv = ((const V*)xp)[i];
-				V gv = xv;
-				if (USE_G) gv = ((const V*)gp)[i];
-#pragma unroll
-				for (int e = 0; e < W; e++) s += f((float)xv[e], USE_G ? (float)gv[e] : 0.f, c);
-			}
-		} else
-			for (long i = lane; i < inner; i += 64) s += f((float)xp[i], USE_G ? (float)gp[i] : 0.f, c);
-		for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-		if (lane == 0) partial[pl] = s;
-	}
-}
-// Folding per-slice (per-plane) partials into per-channel sums, fixed order.  A workgroup is 16 channels x 16 phases: thread
-// (phase = t >> 4, channel = t & 15) adds the slices phase, phase + 16, ... with four independent running sums (four loads in
-// flight; one thread per channel walking every slice with one dependent add chain was 66 us per call, 64 channels x 4 phases
-// still 32 - 68 us on the DawnNet / ResNet-50 steps -- as long as the sweeps over the tensors these folds finish); the 16
-// phases meet in LDS.  FOLD_CH channels per workgroup also means 4x the workgroups of the 64-channel form.
-// out0[c] (+)= sum_i p0[i][c]  and, when p1 is given, out1[c] (+)= sum_i p1[i][c]  (blockIdx.y picks the array)
-__global__ void __launch_bounds__(256) chan_fold_kernel(const float* p0, const float* p1, const long slices, const int C, float* out0, float* out1, const int accumulate)
-{
-	__shared__ float red[FOLD_PH][FOLD_CH];
-	const int ch = threadIdx.x & (FOLD_CH - 1), phase = threadIdx.x / FOLD_CH;
-	const int c = blockIdx.x * FOLD_CH + ch;
-	const float* const p = blockIdx.y ? p1 : p0;
-	float* const out = blockIdx.y ? out1 : out0;
-	red[phase][ch] = c < C ? fold_slices(p, slices, C, c, phase) : 0.f;
-	__syncthreads();
-	if (phase == 0 && c < C) {
-		const float v = fold_phases(red, ch);
-		out[c] = accumulate ? out[c] + v : v;
-	}
-}
-
-template <class F, bool USE_G, class T = float>
-static int chan_reduce(F f, const T* x, const T* g, const chan_view_t& v, float* out, ccv_nnc_stream_context_t* ctx, const int accumulate = 0)
-{
-	hipStream_t stream = stream_of(ctx);
-	long slices;
-	float* partial;
-	if (v.inner == 1) {
-		const int col_tiles = (v.C + RC_COLS - 1) / RC_COLS;
-		slices = ((long)device_cu_count() * 4 + col_tiles - 1) / col_tiles;
-		const long max_slices = (v.outer + 63) / 64;
-		if (slices > max_slices) slices = max_slices;
-		if (slices < 1) slices = 1;
-		const long rps = (v.outer + slices - 1) / slices;
-		slices = v.outer > 0 ? (v.outer + rps - 1) / rps : 1;
-		partial = (float*)workspace_of(ctx, sizeof(float) * (size_t)slices * v.C);
-		if (!partial) return CCV_NNC_EXEC_OOM;
-		hipLaunchKernelGGL(HIP_KERNEL_NAME(chan_reduce_rows_kernel<F, USE_G, T>), dim3(col_tiles, (unsigned)slices), dim3(256), 0, stream, f, x, g, v.outer, v.C, rps > 0 ? rps : 1, partial);
-	} else {
-		slices = v.outer;
-		partial = (float*)workspace_of(ctx, sizeof(float) * (size_t)slices * v.C);
-		if (!partial) return CCV_NNC_EXEC_OOM;
-		const long planes = v.outer * v.C;
-		hipLaunchKernelGGL(HIP_KERNEL_NAME(chan_reduce_planes_kernel<F, USE_G, T>), dim3(plane_grid(planes)), dim3(256), 0, stream, f, x, g, v.C, v.inner, planes, partial);
-	}
-	HIP_ENFORCE(hipGetLastError());
-	hipLaunchKernelGGL(chan_fold_kernel, dim3((v.C + FOLD_CH - 1) / FOLD_CH), dim3(256), 0, stream, (const float*)partial, (const float*)0, slices, v.C, out, (float*)0, accumulate);
-	HIP_ENFORCE(hipGetLastError());
-	return CCV_NNC_EXEC_SUCCESS;
-}
 
 // ---- NCHW-style layouts (inner > 1): ONE WAVE PER PLANE -----------------------------------------------------------------------
 // The ResNet trainer's tensors (N x C x H x W): a channel's elements are N planes of H * W contiguous floats.  A wave walks
@@ -274,15 +167,6 @@ __global__ void __launch_bounds__(256) bn_plane_back_stats_kernel(const T* __res
 }
 // lanes per plane of the batch-norm plane kernels: 16 (four planes per wave) for planes of at most 1 KB
 template <class T> static int plane_lanes(const long inner) { return tune(TUNE_BN_SMALL_PLANES) && inner * (long)sizeof(T) <= 1024 ? 16 : 64; }
-static unsigned plane_grid(const long planes)
-{
-	// one plane per wave over the WHOLE tensor, no grid-stride cap (round 3): the same lesson as the element-wise maps (section 3.2 of DESIGN.md -- a few
-	// thousand workgroups striding a multi-GB tensor keep DRAM pages from all over it in flight, a front of workgroups walking it in order does not; the
-	// capped form ran the batch-norm passes at ~3.4 TB/s).  TUNE_GRID_WG_PER_CU > 0 restores a cap.
-	const long want = (planes + 3) / 4, per_cu = tune(TUNE_GRID_WG_PER_CU);
-	const long cap = per_cu > 0 ? (long)device_cu_count() * per_cu : 0x7fffffffL;
-	return (unsigned)(want < cap ? (want > 0 ? want : 1) : cap);
-}
 
 // ---- per-channel finishing steps (C elements each) ---------------------------------------------------------------------
 // after the sum pass: saved_mean = sum / B; running mean = m * mean + (1 - m) * saved_mean      (batch_norm_cpu_ref.c:67-72)
@@ -774,7 +658,7 @@ static int bnorm_forw_t(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, cons
 	float* var = inputs[4]->data.f32;
 	const int cb = (v.C + 255) / 256;
 	// per-channel affine lives in front of the reduction partials in the workspace
-	WorkspaceScope ws(stream_context, sizeof(float) * 2 * (size_t)v.C, sizeof(float) * (size_t)v.C * (size_t)(v.inner == 1 ? (long)device_cu_count() * 4 + 64 : 2 * v.outer));
+	WorkspaceScope ws(stream_context, sizeof(float) * 2 * (size_t)v.C, v.inner == 1 ? colsum_workspace_bound(v.C) : 2 * chan_planes_workspace_bytes(v.outer, v.C));
 	float* nscale = (float*)ws.prefix();
 	if (!nscale) return CCV_NNC_EXEC_OOM;
 	float* nbias = nscale + v.C;
@@ -806,7 +690,7 @@ static int bnorm_forw_t(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, cons
 		}
 		if (v.inner > 1) { // planes: one sweep from HBM for both statistics (see bn_plane_stats_kernel)
 			const long planes = v.outer * v.C;
-			float* const psum = (float*)workspace_of(stream_context, sizeof(float) * 2 * (size_t)planes);
+			float* const psum = (float*)workspace_of(stream_context, 2 * chan_planes_workspace_bytes(v.outer, v.C));
 			if (!psum) return CCV_NNC_EXEC_OOM;
 			{
 				constexpr int W = 16 / (int)sizeof(T);
@@ -903,13 +787,13 @@ static int bnorm_back_t(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, cons
 	}
 	if (v.inner > 1) { // planes: both sums in one sweep over (x, g)
 		const long planes = v.outer * v.C;
-		float* const pg = (float*)workspace_of(stream_context, sizeof(float) * 2 * (size_t)planes);
+		float* const pg = (float*)workspace_of(stream_context, 2 * chan_planes_workspace_bytes(v.outer, v.C));
 		if (!pg) return CCV_NNC_EXEC_OOM;
 		hipStream_t st = stream_of(stream_context);
 		if (plane_lanes<T>(v.inner) == 16) hipLaunchKernelGGL(HIP_KERNEL_NAME(bn_plane_back_stats_kernel<T, 16>), dim3(plane_grid((planes + 3) / 4)), dim3(256), 0, st, xp, gp, planes, v.C, v.inner, (const float*)saved_mean->data.f32, (const float*)saved_inv_std->data.f32, pg, pg + planes);
 		else hipLaunchKernelGGL(HIP_KERNEL_NAME(bn_plane_back_stats_kernel<T, 64>), dim3(plane_grid(planes)), dim3(256), 0, st, xp, gp, planes, v.C, v.inner, (const float*)saved_mean->data.f32, (const float*)saved_inv_std->data.f32, pg, pg + planes);
 		HIP_ENFORCE(hipGetLastError());
-		hipLaunchKernelGGL(chan_fold_kernel, dim3((v.C + FOLD_CH - 1) / FOLD_CH, 2), dim3(256), 0, st, (const float*)pg, (const float*)(pg + planes), v.outer, v.C, dbias->data.f32, dscale->data.f32, 0);
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(chan_fold_kernel<float>), dim3((v.C + FOLD_CH - 1) / FOLD_CH, 2), dim3(256), 0, st, (const float*)pg, (const float*)(pg + planes), v.outer, v.C, dbias->data.f32, dscale->data.f32, 0);
 		HIP_ENFORCE(hipGetLastError());
 	} else {
 	if ((ret = chan_reduce<RSum, false, T>(RSum(), gp, (const T*)0, v, dbias->data.f32, stream_context)) != CCV_NNC_EXEC_SUCCESS) return ret;
@@ -939,14 +823,6 @@ static int _bnorm_back(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const
 } // namespace
 
 extern "C" long nnc_mi355x_debug_bn_cluster_launches(void) { return g_bn_cluster_launches; }
-
-// out[c] (+)= sum over (o, i) of x[(o * C + c) * inner + i]: the bias gradient of a convolution on NCHW tensors (cmd_conv.cpp)
-int nnc::chan_sum_planes(const float* x, long outer, int C, long inner, float* out, int accumulate, ccv_nnc_stream_context_t* ctx)
-{
-	chan_view_t v;
-	v.outer = outer; v.C = C; v.inner = inner;
-	return chan_reduce<RSum, false, float>(RSum(), x, (const float*)0, v, out, ctx, accumulate);
-}
 
 #define NNC_REG(CMD, BACKEND, FORMATS, DATATYPES, MEMORY, EXEC) \
 	extern "C" void _register_command_##CMD##_backend_##BACKEND(ccv_nnc_cmd_backend_registry_t* const registry) \

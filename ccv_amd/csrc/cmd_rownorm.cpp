@@ -10,7 +10,7 @@
 // n elements (or a single one); other reduce-axis patterns return CCV_NNC_EXEC_INVALID.  One 256-thread block per row; a row is read from
 // HBM once and re-read from L1/L2 for the later passes; parameter gradients are row-chunk partial sums folded by colsum_f32 (fixed order).
 // HBM-bound: forward 2 |a|, backward 3 |a| bytes.
-#include "common.h"
+#include "chan_sums.h"
 
 using namespace nnc;
 
@@ -159,7 +159,7 @@ static int rownorm_back(const ccv_nnc_tensor_t* g, const ccv_nnc_tensor_t* a, co
 		const int rows_per_chunk = (rows + chunks - 1) / chunks;
 		chunks = (rows + rows_per_chunk - 1) / rows_per_chunk;
 		// [ colsum_f32's own partials (it takes the workspace base) | our chunk partials ]
-		const size_t head = (sizeof(float) * (size_t)device_cu_count() * 4 * n + 255) & ~(size_t)255;
+		const size_t head = (colsum_workspace_bytes(chunks, n) + 255) & ~(size_t)255;
 		char* ws = (char*)workspace_of(ctx, head + sizeof(float) * (size_t)chunks * n);
 		if (!ws) return CCV_NNC_EXEC_OOM;
 		float* partial = (float*)(ws + head);

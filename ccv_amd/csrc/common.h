@@ -197,15 +197,19 @@ int transpose_half(const void* in, void* out, int batch, int R, int C, ccv_nnc_s
 // CCV_NNC_EXEC_NO_KERNEL: the tensor is not in whole 16-byte chunks -- nothing was launched, the caller takes the two separate passes.
 int transpose_half_rowsum(const void* in, void* out, int batch, int R, int C, float* row_partial, ccv_nnc_stream_context_t* ctx);
 inline long transpose_half_rowsum_slices(const int batch, const int C) { return (long)batch * ((C + 63) / 64); }
+int fill_f32(float* p, size_t n, float v, ccv_nnc_stream_context_t* ctx); // (cmd_ew.cpp)
 int relu_inplace(ccv_nnc_tensor_t* t, ccv_nnc_stream_context_t* ctx); // t = max(t, 0), dense CCV_32F / CCV_16F (cmd_ew.cpp)
 int relu_back_inplace(ccv_nnc_tensor_t* h, const ccv_nnc_tensor_t* b, ccv_nnc_stream_context_t* ctx); // h = b > 0 ? h : 0, dense, same type and count
 int weights_nchw_to_nhwc(const float* w, float* out, int K, int C, int khw, ccv_nnc_stream_context_t* ctx);
 int weights_nhwc_to_nchw(const float* w, float* out, int K, int C, int khw, ccv_nnc_stream_context_t* ctx);
 
-// Shared device helpers (cmd_ew.cpp).
-int colsum_f32(const float* x, long rows, int cols, long ld, float* out, int accumulate, ccv_nnc_stream_context_t* ctx); // out[c] (+)= sum_r x[r*ld + c]
-int fill_f32(float* p, size_t n, float v, ccv_nnc_stream_context_t* ctx);
-int chan_sum_planes(const float* x, long outer, int C, long inner, float* out, int accumulate, ccv_nnc_stream_context_t* ctx); // cmd_norm.cpp: out[c] (+)= sum_{o,i} x[(o * C + c) * inner + i]
+// Column and channel sums (chan_sums.cpp): fp32 partials at the BASE of the stream workspace, folded in a fixed order; halves are summed in fp32 and rounded once.
+// A caller with data of its own in the workspace keeps it behind a head sized by chan_sums.h (colsum_workspace_bytes / _bound, chan_planes_workspace_bytes).
+int colsum_f32(const float* x, long rows, int cols, long ld, float* out, int accumulate, ccv_nnc_stream_context_t* ctx); // out[c] (+)= sum_r x[r * ld + c]
+int colsum_f16(const void* x, long rows, int cols, long ld, void* out, int accumulate, ccv_nnc_stream_context_t* ctx);   // the same on halves
+int colsum_partials_f16(const float* partial, long slices, int cols, void* out, int accumulate, ccv_nnc_stream_context_t* ctx); // out[c] (+)= sum_s partial[s * cols + c]; `partial` has room for colsum_partials_bytes(slices, cols): a second, grouped level
+int chan_sum_planes(const float* x, long outer, int C, long inner, float* out, int accumulate, ccv_nnc_stream_context_t* ctx); // out[c] (+)= sum_{o,i} x[(o * C + c) * inner + i]
+int chan_sum_planes_f16(const void* x, long outer, int C, long inner, void* out, int accumulate, ccv_nnc_stream_context_t* ctx); // the same on halves
 
 // Optional in-library kernel timing (bench.py roofline leg): when enabled, a ProfScope brackets ONE kernel launch with
 // HIP events on the stream the kernel is launched on and files (name, algorithmic flops/bytes, problem dims).
@@ -305,9 +309,6 @@ static int half_staged(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const
 bool any_half_tensor(ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size);
 int half_to_float(const void* in, float* out, size_t n, ccv_nnc_stream_context_t* ctx);
 int float_to_half(const float* in, void* out, size_t n, ccv_nnc_stream_context_t* ctx);
-int chan_sum_planes_f16(const void* x, long outer, int C, long inner, void* out, int accumulate, ccv_nnc_stream_context_t* ctx);
-int colsum_f16(const void* x, long rows, int cols, long ld, void* out, int accumulate, ccv_nnc_stream_context_t* ctx); // halves: out[c] (+)= sum_r x[r * ld + c], fp32 sums
-int colsum_partials_f16(const float* partial, long slices, int cols, void* out, int accumulate, ccv_nnc_stream_context_t* ctx); // out[c] (+)= sum_s partial[s * cols + c], slices in a fixed order, rounded to half once; `partial` has room for (slices + 256) * cols floats (a second, grouped level)
 
 // Palettized inputs (palette.cpp): rows whose reference counterparts list CCV_QX (GEMM, convolution, transposed convolution, attention's head projection) run
 // on dense images of their CCV_QX inputs.  NNC_DEPALETTIZED(registry, EXEC) adds CCV_QX to the row and routes it through the wrapper (a plain call of EXEC

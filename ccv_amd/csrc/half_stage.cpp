@@ -93,126 +93,6 @@ int float_to_half(const float* in, void* out, size_t n, ccv_nnc_stream_context_t
 	return CCV_NNC_EXEC_SUCCESS;
 }
 
-// Bias gradients of the half-precision contraction commands.
-// dbias for half precision: out[c] (+)= sum_r x[r * ld + c], fp32 partial sums over row slices, folded in a fixed order
-static __global__ void __launch_bounds__(256) colsum_h_partial_kernel(const half_t* x, const long rows, const int cols, const long ld, const long rows_per_slice, float* partial)
-{
-	__shared__ float red[4][64];
-	const int c = blockIdx.x * 64 + (threadIdx.x & 63), rs = threadIdx.x >> 6;
-	const long r0 = (long)blockIdx.y * rows_per_slice, r1 = r0 + rows_per_slice < rows ? r0 + rows_per_slice : rows;
-	float s = 0.f;
-	if (c < cols) for (long r = r0 + rs; r < r1; r += 4) s += (float)x[r * ld + c];
-	red[rs][threadIdx.x & 63] = s;
-	__syncthreads();
-	if (rs == 0 && c < cols) partial[(long)blockIdx.y * cols + c] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-}
-static __global__ void __launch_bounds__(256) colsum_h_final_kernel(const float* partial, const int slices, const int cols, half_t* out, const int accumulate)
-{
-	__shared__ float red[FOLD_PH][FOLD_CH]; // 16 columns x 16 phases per workgroup (common.h)
-	const int ch = threadIdx.x & (FOLD_CH - 1), phase = threadIdx.x / FOLD_CH;
-	const int c = blockIdx.x * FOLD_CH + ch;
-	red[phase][ch] = c < cols ? fold_slices(partial, slices, cols, c, phase) : 0.f;
-	__syncthreads();
-	if (phase == 0 && c < cols) {
-		const float s = fold_phases(red, ch);
-		out[c] = (half_t)(accumulate ? (float)out[c] + s : s);
-	}
-}
-int colsum_f16(const void* xv, long rows, int cols, long ld, void* outv, int accumulate, ccv_nnc_stream_context_t* ctx)
-{
-	if (cols <= 0) return CCV_NNC_EXEC_SUCCESS;
-	const half_t* x = (const half_t*)xv;
-	half_t* out = (half_t*)outv;
-	const int col_tiles = (cols + 63) / 64;
-	long slices = ((long)device_cu_count() * 4 + col_tiles - 1) / col_tiles;
-	const long max_slices = (rows + 63) / 64;
-	if (slices > max_slices) slices = max_slices;
-	if (slices < 1) slices = 1;
-	const long rows_per_slice = (rows + slices - 1) / slices;
-	slices = rows > 0 ? (rows + rows_per_slice - 1) / rows_per_slice : 1;
-	float* partial = (float*)workspace_of(ctx, sizeof(float) * (size_t)slices * cols);
-	if (!partial) return CCV_NNC_EXEC_OOM;
-	hipStream_t stream = stream_of(ctx);
-	hipLaunchKernelGGL(colsum_h_partial_kernel, dim3(col_tiles, (unsigned)slices), dim3(256), 0, stream, x, rows, cols, ld, rows_per_slice > 0 ? rows_per_slice : 1, partial);
-	HIP_ENFORCE(hipGetLastError());
-	hipLaunchKernelGGL(colsum_h_final_kernel, dim3((cols + FOLD_CH - 1) / FOLD_CH), dim3(256), 0, stream, (const float*)partial, (int)slices, cols, out, accumulate);
-	HIP_ENFORCE(hipGetLastError());
-	return CCV_NNC_EXEC_SUCCESS;
-}
-
-// Many slices (one per image and 64-pixel tile: thousands) are first folded in groups -- a workgroup per (64 columns, group of slices), four slices in flight per
-// column, coalesced rows -- so that the final kernel's per-column chains stay a few loads long.  Fixed order throughout: deterministic.
-static __global__ void __launch_bounds__(256) partials_group_kernel(const float* __restrict__ in, const long slices, const int cols, const int group, float* __restrict__ out)
-{
-	__shared__ float red[4][64];
-	const int cl = threadIdx.x & 63, ph = threadIdx.x >> 6;
-	const int c = blockIdx.x * 64 + cl;
-	const long s0 = (long)blockIdx.y * group, s1 = s0 + group < slices ? s0 + group : slices;
-	float a = 0.f, b = 0.f;
-	if (c < cols) {
-		long i = s0 + ph;
-		for (; i + 4 < s1; i += 8) { a += in[i * cols + c]; b += in[(i + 4) * cols + c]; }
-		if (i < s1) a += in[i * cols + c];
-	}
-	red[ph][cl] = a + b;
-	__syncthreads();
-	if (ph == 0 && c < cols) out[(long)blockIdx.y * cols + c] = (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
-}
-int colsum_partials_f16(const float* partial, long slices, const int cols, void* out, const int accumulate, ccv_nnc_stream_context_t* ctx)
-{
-	if (cols <= 0) return CCV_NNC_EXEC_SUCCESS;
-	if (slices > 0x7fffffffL) return CCV_NNC_EXEC_INVALID;
-	hipStream_t stream = stream_of(ctx);
-	if (slices > 512) { // (the grouped sums go to a second area right behind the partials)
-		const int group = (int)((slices + 255) / 256 < 16 ? 16 : (slices + 255) / 256);
-		const long groups = (slices + group - 1) / group;
-		float* const folded = (float*)partial + (size_t)slices * cols;
-		hipLaunchKernelGGL(partials_group_kernel, dim3((cols + 63) / 64, (unsigned)groups), dim3(256), 0, stream, partial, slices, cols, group, folded);
-		HIP_ENFORCE(hipGetLastError());
-		partial = folded;
-		slices = groups;
-	}
-	hipLaunchKernelGGL(colsum_h_final_kernel, dim3((cols + FOLD_CH - 1) / FOLD_CH), dim3(256), 0, stream, partial, (int)slices, cols, (half_t*)out, accumulate);
-	HIP_ENFORCE(hipGetLastError());
-	return CCV_NNC_EXEC_SUCCESS;
-}
-
-// out[c] (+)= sum over (o, i) of x[(o * C + c) * inner + i] for halves (bias gradient of an NCHW convolution): one workgroup per
-// plane, fp32 partials in the workspace, folded per channel in a fixed order.
-static __global__ void __launch_bounds__(256) plane_sum_h_kernel(const half_t* __restrict__ x, const long planes, const long inner, float* __restrict__ partial)
-{ // a WAVE per plane (8 halves per 16-byte load when the plane allows): a workgroup per plane left 7 x 7 planes with 49 busy threads
-	typedef half_t h8 __attribute__((ext_vector_type(8)));
-	const int lane = threadIdx.x & 63;
-	const long nw = (long)gridDim.x * 4;
-	for (long pl = (long)blockIdx.x * 4 + (threadIdx.x >> 6); pl < planes; pl += nw) {
-		const half_t* const p = x + pl * inner;
-		float s = 0.f;
-		if ((inner & 7) == 0 && (((uintptr_t)p) & 15) == 0) {
-			for (long i = lane; i < (inner >> 3); i += 64) {
-				const h8 v = ((const h8*)p)[i];
-#pragma unroll
-				for (int e = 0; e < 8; e++) s += (float)v[e];
-			}
-		} else
-			for (long i = lane; i < inner; i += 64) s += (float)p[i];
-		for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-		if (lane == 0) partial[pl] = s;
-	}
-}
-int chan_sum_planes_f16(const void* x, long outer, int C, long inner, void* out, int accumulate, ccv_nnc_stream_context_t* ctx)
-{
-	if (C <= 0 || outer <= 0) return CCV_NNC_EXEC_SUCCESS;
-	float* partial = (float*)workspace_of(ctx, sizeof(float) * (size_t)outer * C);
-	if (!partial) return CCV_NNC_EXEC_OOM;
-	hipStream_t stream = stream_of(ctx);
-	const long planes = outer * C, want = (planes + 3) / 4;
-	hipLaunchKernelGGL(plane_sum_h_kernel, dim3((unsigned)(want < 0x7fffffffL ? want : 0x7fffffffL)), dim3(256), 0, stream, (const half_t*)x, planes, inner, partial);
-	HIP_ENFORCE(hipGetLastError());
-	hipLaunchKernelGGL(colsum_h_final_kernel, dim3((C + FOLD_CH - 1) / FOLD_CH), dim3(256), 0, stream, (const float*)partial, (int)outer, C, (half_t*)out, accumulate);
-	HIP_ENFORCE(hipGetLastError());
-	return CCV_NNC_EXEC_SUCCESS;
-}
-
 bool any_half_tensor(ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
 {
 	for (int i = 0; i < input_size; i++)

@@ -476,6 +476,9 @@ void nnc_mi355x_debug_pool_fences(long* events, long* waits);
 /* batch-norm commands that ran on the cluster kernels (cmd_norm.cpp: a cluster of workgroups per channel keeps the channel in registers between the
  * statistics and the apply pass; NNC_MI355X_BN_CLUSTER=0 / nnc_mi355x_tune_set("BN_CLUSTER", 0) selects the plane kernels). */
 long nnc_mi355x_debug_bn_cluster_launches(void);
+/* Test hook for the column sums (chan_sums.cpp), host arithmetic only: the slice plan of a rows x cols sum, the workspace bytes that call requests, and
+ * the most any call with `cols` columns requests -- the head size of callers that keep data of their own behind the partials. */
+void nnc_mi355x_debug_colsum_plan(long rows, int cols, long* slices, long* rows_per_slice, size_t* bytes, size_t* bound);
 /* commands that have reached an exec function of this library since it was loaded (tools/host_resnet_bench.c divides the host's enqueue time by it) */
 long nnc_mi355x_debug_exec_count(void);
 /* Test hook for the CCV_16F datapath (half_stage.cpp): how many half-precision tensors have been given an fp32 image so far
