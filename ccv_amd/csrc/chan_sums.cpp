@@ -24,6 +24,33 @@ size_t colsum_workspace_bytes(const long rows, const int cols) { return sizeof(f
 // and it is reached (rows = 64 * s0 * s0 gives s0 slices of 64 * s0 rows each), so it is the maximum, not an estimate.
 size_t colsum_workspace_bound(const int cols) { return cols > 0 ? sizeof(float) * (size_t)colsum_slices_most((cols + RC_COLS - 1) / RC_COLS) * (size_t)cols : 0; }
 
+// The per-image product sums: the tile width among 8, 16, 32, 64 channel vectors that wastes the fewest lanes on the last tile (the widest of equals; fewer than
+// 8 vectors: the next power of two), then pixel slices until the launch has about four workgroups per CU, none with fewer than four pixels per phase.
+scaled_rows_plan_t scaled_rows_plan(const int N, const int cv, const long P)
+{
+	scaled_rows_plan_t sp;
+	sp.cvt_log2 = 0;
+	if (cv < 8) { while ((1 << sp.cvt_log2) < cv) sp.cvt_log2++; }
+	else {
+		long best = -1;
+		for (int l = 3; l <= 6; l++) {
+			const long w = 1L << l, covered = w * ((cv + w - 1) / w);
+			if (best < 0 || covered * 1 <= best) { best = covered; sp.cvt_log2 = l; }
+		}
+	}
+	const int cvt = 1 << sp.cvt_log2, phases = 256 / cvt;
+	sp.tiles = (cv + cvt - 1) / cvt;
+	const long wgs = (long)N * sp.tiles;
+	long slices = wgs > 0 ? ((long)device_cu_count() * 4 + wgs - 1) / wgs : 1;
+	const long max_slices = (P + 4L * phases - 1) / (4L * phases);
+	if (slices > max_slices) slices = max_slices;
+	if (slices < 1) slices = 1;
+	sp.rows_per_slice = (P + slices - 1) / slices;
+	if (sp.rows_per_slice < 1) sp.rows_per_slice = 1;
+	sp.slices = P > 0 ? (P + sp.rows_per_slice - 1) / sp.rows_per_slice : 1;
+	return sp;
+}
+
 // Many slices (one per image and 64-pixel tile: thousands) are first folded in groups -- a workgroup per (64 columns, group of slices), four slices in flight per
 // column, coalesced rows -- so that the final kernel's per-column chains stay a few loads long.  Fixed order throughout: deterministic.
 struct partials_groups_t { int group; long groups; }; // groups == 0: few enough slices for the fold alone

@@ -7,6 +7,7 @@
 //     behind the partials takes its head size from these functions, never from a restatement of the plan;
 //   * the kernel templates: rows (lanes = 64 consecutive columns), planes (a wave per plane), the fold (fp32 or half output, an optional second array);
 //   * chan_reduce, the launcher over a [outer][C][inner] view with the batch-norm functors (cmd_norm.cpp uses it with all three);
+//   * the per-image column sums of a product of two tensors (scaled_rows_image_kernel: MUL's gradient towards a per-(image, channel) operand, mul_planes.h);
 //   * chan_sums.cpp: the 16-byte float rows kernel, the grouped level for thousands of slices, and the five exported sums declared in common.h.
 // The route decides the order of the additions and so the bits: see each launcher for which kernel it takes when.
 #pragma once
@@ -95,6 +96,63 @@ __global__ void __launch_bounds__(256) chan_fold_kernel(const float* p0, const f
 		const float v = fold_phases(red, ch);
 		out[c] = (TO)(accumulate ? (float)out[c] + v : v);
 	}
+}
+
+// Per-IMAGE column sums of a product, 16-byte lanes: partial[slice][n][c] = sum over the slice's pixels r of (p g[n][r][c]) x[n][r][c] and, DL, on the way
+// d[n][r][c] = (p g[n][r][c]) s[n][c] -- g and x are read once for both.  (The rows kernel above sums ONE matrix: a launch per image would be 2 N launches.)
+// grid (channel-vector tiles, pixel slices, N); a workgroup is `cvt` channel vectors (a power of two) x 256 / cvt pixel phases; the phases meet in LDS, in order.
+// The slices are folded by chan_fold_kernel over N * C columns.
+struct scaled_rows_plan_t { int cvt_log2, tiles; long slices, rows_per_slice; };
+scaled_rows_plan_t scaled_rows_plan(int N, int cv, long P); // cv = channel vectors per pixel
+template <class T, bool DL>
+__global__ void __launch_bounds__(256) scaled_rows_image_kernel(const T* g, const T* x, const T* s, T* d, float* partial, const float p, const int cv, const int cvt_log2, const unsigned P, const unsigned rows_per_slice)
+{
+	constexpr int W = 16 / sizeof(T);
+	typedef typename pack16<T>::type V;
+	__shared__ float red[256 * W];
+	const int cvt = 1 << cvt_log2, q = threadIdx.x & (cvt - 1), phase = threadIdx.x >> cvt_log2, phases = 256 >> cvt_log2;
+	const int c = blockIdx.x * cvt + q, n = blockIdx.z, N = gridDim.z;
+	const unsigned r0 = blockIdx.y * rows_per_slice, r1 = r0 + rows_per_slice < P ? r0 + rows_per_slice : P;
+	float acc[W];
+#pragma unroll
+	for (int e = 0; e < W; e++) acc[e] = 0.f;
+	if (c < cv) {
+		V sv = {};
+		if (DL) sv = ((const V*)s)[(size_t)n * cv + c];
+		for (unsigned r = r0 + phase; r < r1; r += phases) {
+			const size_t i = ((size_t)n * P + r) * cv + c;
+			const V gv = ((const V*)g)[i], xv = ((const V*)x)[i];
+			V o;
+#pragma unroll
+			for (int e = 0; e < W; e++) {
+				const float pg = p * (float)gv[e];
+				acc[e] += pg * (float)xv[e];
+				if (DL) o[e] = (T)f32_rounded(pg * (float)sv[e]);
+			}
+			if (DL) ((V*)d)[i] = o;
+		}
+	}
+#pragma unroll
+	for (int e = 0; e < W; e++) red[threadIdx.x * W + e] = acc[e];
+	__syncthreads();
+	if (phase == 0 && c < cv) {
+		float* const out = partial + ((size_t)blockIdx.y * N + n) * ((size_t)cv * W) + (size_t)c * W;
+#pragma unroll
+		for (int e = 0; e < W; e++) {
+			float t = red[q * W + e];
+			for (int ph = 1; ph < phases; ph++) t += red[((ph << cvt_log2) + q) * W + e];
+			out[e] = t;
+		}
+	}
+}
+template <class T>
+static void scaled_rows_image_launch(const scaled_rows_plan_t& sp, const T* g, const T* x, const T* s, T* d, float* partial, const float p, const int N, const int C, const unsigned P, hipStream_t stream)
+{
+	const int cv = C / (int)(16 / sizeof(T));
+	const dim3 grid(sp.tiles, (unsigned)sp.slices, N);
+	if (d) hipLaunchKernelGGL(HIP_KERNEL_NAME(scaled_rows_image_kernel<T, true>), grid, dim3(256), 0, stream, g, x, s, d, partial, p, cv, sp.cvt_log2, P, (unsigned)sp.rows_per_slice);
+	else hipLaunchKernelGGL(HIP_KERNEL_NAME(scaled_rows_image_kernel<T, false>), grid, dim3(256), 0, stream, g, x, s, d, partial, p, cv, sp.cvt_log2, P, (unsigned)sp.rows_per_slice);
+	HIP_ENFORCE(hipGetLastError());
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------------------------------

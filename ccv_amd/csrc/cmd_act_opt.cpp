@@ -1,5 +1,6 @@
 // Activations, plain softmax and the Adam / AdamW / RMSProp update on gfx950 -- the element-wise rows the reference's other
-// trainers need beside SGD.  All HBM-bound: grid-stride, 16 bytes per lane when aligned.
+// trainers need beside SGD.  All HBM-bound: grid-stride, 16 bytes per lane when aligned.  The five activation families run
+// CCV_16F tensors as halves themselves (act_map_kernel; half_stage.cpp g_native_half, tunable ACT_HALF_NATIVE).
 // Oracle semantics (CPU reference, fp32 storage, arithmetic promoted to double there; float here, within 1e-6):
 //   sigmoid     lib/nnc/cmd/sigmoid/ccv_nnc_sigmoid_cpu_ref.c:13-66        b = 1/(1+e^-a);  h = g b (1-b)      (g may be absent: ones)
 //   tanh        lib/nnc/cmd/tanh/ccv_nnc_tanh_cpu_ref.c:13-62              b = tanh a;      h = g (1-b^2)
@@ -19,29 +20,47 @@ namespace {
 
 constexpr int EW_THREADS = 256;
 
-// out[i] = f(x[i], y[i]) over contiguous fp32 tensors; NIN = how many inputs are read
-template <class F, int NIN>
-__global__ void __launch_bounds__(EW_THREADS) act_map_kernel(F f, float* out, const float* in0, const float* in1, const size_t n4, const size_t n)
+// out[i] = f(x[i], y[i]) over contiguous tensors of one element type; NIN = how many inputs are read.  T = float, or _Float16 for the CCV_16F tensors of the
+// half-precision trainers: loaded and stored as halves (a lane takes 16 bytes: 4 floats / 8 halves), the functors below compute in fp32 as they always did and the
+// result is rounded once, to nearest even, by the store.  nv = whole 16-byte vectors (0 when a base is not 16-byte aligned: every element takes the scalar loop).
+typedef _Float16 half_t;
+template <class T> struct pack16 { typedef T type __attribute__((ext_vector_type(16 / sizeof(T)))); };
+template <class F, int NIN, class T>
+__global__ void __launch_bounds__(EW_THREADS) act_map_kernel(F f, T* out, const T* in0, const T* in1, const size_t nv, const size_t n)
 {
+	constexpr int W = 16 / sizeof(T);
+	typedef typename pack16<T>::type V;
 	const size_t stride = (size_t)gridDim.x * blockDim.x;
 	const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	for (size_t i = tid; i < n4; i += stride) {
-		const float4 a = ((const float4*)in0)[i];
-		const float4 b = NIN > 1 ? ((const float4*)in1)[i] : make_float4(0, 0, 0, 0);
-		((float4*)out)[i] = make_float4(f(a.x, b.x), f(a.y, b.y), f(a.z, b.z), f(a.w, b.w));
+	for (size_t i = tid; i < nv; i += stride) {
+		const V a = ((const V*)in0)[i];
+		V b = a;
+		if (NIN > 1) b = ((const V*)in1)[i];
+		V r;
+#pragma unroll
+		for (int e = 0; e < W; e++) r[e] = (T)f32_rounded(f((float)a[e], NIN > 1 ? (float)b[e] : 0.f));
+		((V*)out)[i] = r;
 	}
-	for (size_t i = n4 * 4 + tid; i < n; i += stride) out[i] = f(in0[i], NIN > 1 ? in1[i] : 0.f);
+	for (size_t i = nv * W + tid; i < n; i += stride) out[i] = (T)f32_rounded(f((float)in0[i], NIN > 1 ? (float)in1[i] : 0.f));
 }
 
-template <class F, int NIN>
-static int act_map(F f, float* out, const float* in0, const float* in1, const size_t n, ccv_nnc_stream_context_t* ctx)
+template <class F, int NIN, class T>
+static int act_map(F f, T* out, const T* in0, const T* in1, const size_t n, ccv_nnc_stream_context_t* ctx)
 {
 	if (n == 0) return CCV_NNC_EXEC_SUCCESS;
+	constexpr int W = 16 / sizeof(T);
 	const bool vec = aligned16(out) && aligned16(in0) && (NIN < 2 || aligned16(in1));
-	const size_t n4 = vec ? n / 4 : 0;
-	hipLaunchKernelGGL(HIP_KERNEL_NAME(act_map_kernel<F, NIN>), dim3(grid_for(vec ? n4 + 3 : n, EW_THREADS)), dim3(EW_THREADS), 0, stream_of(ctx), f, out, in0, in1, n4, n);
+	const size_t nv = vec ? n / W : 0;
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(act_map_kernel<F, NIN, T>), dim3(grid_for(vec ? nv + (W - 1) : n, EW_THREADS)), dim3(EW_THREADS), 0, stream_of(ctx), f, out, in0, in1, nv, n);
 	HIP_ENFORCE(hipGetLastError());
 	return CCV_NNC_EXEC_SUCCESS;
+}
+// the tensors' own element type: every tensor handed over is of one type (half_stage.cpp keeps the tensors of these rows in half precision only when all of them are)
+template <class F, int NIN>
+static int act_map_any(F f, const int datatype, ccv_nnc_tensor_t* out, const ccv_nnc_tensor_t* in0, const ccv_nnc_tensor_t* in1, const size_t n, ccv_nnc_stream_context_t* ctx)
+{
+	if (CCV_GET_DATA_TYPE(datatype) == CCV_16F) return act_map<F, NIN, half_t>(f, (half_t*)out->data.u8, (const half_t*)in0->data.u8, in1 ? (const half_t*)in1->data.u8 : 0, n, ctx);
+	return act_map<F, NIN, float>(f, out->data.f32, (const float*)in0->data.f32, in1 ? (const float*)in1->data.f32 : 0, n, ctx);
 }
 
 __device__ __forceinline__ float sigmoidf_(const float x) { return 1.f / (1.f + expf(-x)); }
@@ -79,31 +98,45 @@ struct OpLeakyBack { float s; __device__ float operator()(float b, float g) cons
 
 static bool same_count(const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* b) { return tensor_count(a->info) == tensor_count(b->info); }
 static bool dense_f32(const ccv_nnc_tensor_t* t) { return t && tensor_contiguous(t) && CCV_GET_DATA_TYPE(t->info.datatype) == CCV_32F; }
+// dense, and of datatype dt
+static bool dense_of(const ccv_nnc_tensor_t* t, const int dt) { return t && tensor_contiguous(t) && CCV_GET_DATA_TYPE(t->info.datatype) == dt; }
+// CCV_32F or CCV_16F (the latter only ever arrives when half_stage.cpp's table handed ALL of the command's tensors over as halves), else 0
+static int float_type(const ccv_nnc_tensor_t* t)
+{
+	const int dt = t ? CCV_GET_DATA_TYPE(t->info.datatype) : 0;
+	return dt == CCV_32F || dt == CCV_16F ? dt : 0;
+}
 
 // forward: inputs[0] = a -> outputs[0] = b
 template <class F>
 static int unary_forw(F f, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const ctx)
 {
-	if (input_size < 1 || output_size < 1 || !dense_f32(inputs[0]) || !dense_f32(outputs[0]) || !same_count(inputs[0], outputs[0])) return CCV_NNC_EXEC_INVALID;
-	return act_map<F, 1>(f, outputs[0]->data.f32, inputs[0]->data.f32, 0, tensor_count(inputs[0]->info), ctx);
+	if (input_size < 1 || output_size < 1) return CCV_NNC_EXEC_INVALID;
+	const int dt = float_type(inputs[0]);
+	if (!dt || !dense_of(inputs[0], dt) || !dense_of(outputs[0], dt) || !same_count(inputs[0], outputs[0])) return CCV_NNC_EXEC_INVALID;
+	return act_map_any<F, 1>(f, dt, outputs[0], inputs[0], 0, tensor_count(inputs[0]->info), ctx);
 }
 // backward from the forward OUTPUT: inputs (g [may be null], _, b) -> h
 template <class F, class FONES>
 static int back_from_output(F f, FONES fones, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const ctx)
 {
-	if (input_size < 3 || output_size < 1 || !dense_f32(inputs[2]) || !dense_f32(outputs[0]) || !same_count(inputs[2], outputs[0])) return CCV_NNC_EXEC_INVALID;
+	if (input_size < 3 || output_size < 1) return CCV_NNC_EXEC_INVALID;
+	const int dt = float_type(inputs[2]);
+	if (!dt || !dense_of(inputs[2], dt) || !dense_of(outputs[0], dt) || !same_count(inputs[2], outputs[0])) return CCV_NNC_EXEC_INVALID;
 	const ccv_nnc_tensor_t* g = inputs[0];
 	const size_t n = tensor_count(inputs[2]->info);
-	if (!g) return act_map<FONES, 1>(fones, outputs[0]->data.f32, inputs[2]->data.f32, 0, n, ctx);
-	if (!dense_f32(g) || !same_count(g, outputs[0])) return CCV_NNC_EXEC_INVALID;
-	return act_map<F, 2>(f, outputs[0]->data.f32, inputs[2]->data.f32, g->data.f32, n, ctx);
+	if (!g) return dt == CCV_32F ? act_map<FONES, 1, float>(fones, outputs[0]->data.f32, (const float*)inputs[2]->data.f32, 0, n, ctx) : CCV_NNC_EXEC_INVALID; // (halves without g: fp32 images, half_stage.cpp)
+	if (!dense_of(g, dt) || !same_count(g, outputs[0])) return CCV_NNC_EXEC_INVALID;
+	return act_map_any<F, 2>(f, dt, outputs[0], inputs[2], g, n, ctx);
 }
 // backward from the forward INPUT: inputs (g, a) -> h
 template <class F>
 static int back_from_input(F f, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const ctx)
 {
-	if (input_size < 2 || output_size < 1 || !dense_f32(inputs[0]) || !dense_f32(inputs[1]) || !dense_f32(outputs[0]) || !same_count(inputs[0], inputs[1]) || !same_count(inputs[0], outputs[0])) return CCV_NNC_EXEC_INVALID;
-	return act_map<F, 2>(f, outputs[0]->data.f32, inputs[1]->data.f32, inputs[0]->data.f32, tensor_count(inputs[0]->info), ctx);
+	if (input_size < 2 || output_size < 1) return CCV_NNC_EXEC_INVALID;
+	const int dt = float_type(inputs[0]);
+	if (!dt || !dense_of(inputs[0], dt) || !dense_of(inputs[1], dt) || !dense_of(outputs[0], dt) || !same_count(inputs[0], inputs[1]) || !same_count(inputs[0], outputs[0])) return CCV_NNC_EXEC_INVALID;
+	return act_map_any<F, 2>(f, dt, outputs[0], inputs[1], inputs[0], tensor_count(inputs[0]->info), ctx);
 }
 
 #define EXEC_ARGS const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context

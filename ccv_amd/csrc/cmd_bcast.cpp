@@ -13,7 +13,9 @@
 //                        element, serial over the reduced sub-space: deterministic and in the reference's summation order.
 //                        (Reductions on the training hot path -- bias gradients, batch-norm statistics -- do NOT come
 //                        through here: they use the two-stage column reducers of cmd_ew.cpp / cmd_norm.cpp.)
+// One pattern of MUL leaves them: an activation tensor times one value per (image, channel), the squeeze-excite scale -- mul_planes.h, mul_planes_plan below.
 #include "common.h"
+#include "mul_planes.h"
 #include <math.h>
 
 using namespace nnc;
@@ -252,8 +254,75 @@ static int _add_back(EXEC_ARGS)
 	}
 	return CCV_NNC_EXEC_SUCCESS;
 }
+// ---- MUL on the plane-scale kernels (mul_planes.h) ---------------------------------------------------------------------------------------------------
+// The pattern: a dense 4-d tensor [N][C][H][W] (NHWC: [N][H][W][C]) and one of the same extents on batch and channel with 1 x 1 spatial extents, either as
+// the first or the second operand; every tensor dense, of ONE element type (CCV_32F, or CCV_16F when half_stage.cpp left them in place) and one format;
+// the large tensors 16-byte aligned; no accumulation; g present.  Anything else is not this path and keeps the generic kernels.
+struct mul_plan_t {
+	mul_planes_geom_t m;
+	int dt, first; // first: the small operand is a (input 0 forward, input 1 backward)
+	const ccv_nnc_tensor_t *big, *small, *g;
+	ccv_nnc_tensor_t *out, *dbig, *dsmall;
+};
+static bool mp_dense(const ccv_nnc_tensor_t* t, const int dt, const int format) { return t && !CCV_IS_TENSOR_VIEW(t) && CCV_GET_DATA_TYPE(t->info.datatype) == dt && t->info.format == format && tensor_nd(t->info.dim) == 4; }
+static bool mp_same_dims(const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* b) { for (int i = 0; i < 4; i++) if (a->info.dim[i] != b->info.dim[i]) return false; return true; }
+static bool mp_pair(const ccv_nnc_tensor_t* big, const ccv_nnc_tensor_t* small, mul_plan_t* o)
+{
+	if (!big || !small) return false;
+	const int dt = CCV_GET_DATA_TYPE(big->info.datatype), format = big->info.format;
+	if ((dt != CCV_32F && dt != CCV_16F) || (format != CCV_TENSOR_FORMAT_NCHW && format != CCV_TENSOR_FORMAT_NHWC)) return false;
+	if (!mp_dense(big, dt, format) || !mp_dense(small, dt, format) || !aligned16(big->data.u8)) return false;
+	const int nhwc = format == CCV_TENSOR_FORMAT_NHWC;
+	const int* const d = big->info.dim;
+	const int* const e = small->info.dim;
+	const int N = d[0], C = nhwc ? d[3] : d[1], H = nhwc ? d[1] : d[2], Wd = nhwc ? d[2] : d[3];
+	if (e[0] != N || (nhwc ? e[3] : e[1]) != C || (nhwc ? e[1] : e[2]) != 1 || (nhwc ? e[2] : e[3]) != 1) return false;
+	const long P = (long)H * Wd;
+	if (N < 1 || C < 1 || P < 2 || P > MUL_PLANES_MAX_PLANE || N > 65535 || (double)N * C * (double)P >= 2147483648.0) return false; // (P == 1: the operands have one shape, nothing is broadcast)
+	if (nhwc && (C % (int)(16 / datatype_size(dt)) != 0 || !aligned16(small->data.u8))) return false;
+	o->m.nhwc = nhwc; o->m.N = N; o->m.C = C; o->m.P = (unsigned)P;
+	o->dt = dt; o->big = big; o->small = small;
+	return true;
+}
+static bool mul_planes_plan(const ccv_nnc_cmd_t cmd, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, mul_plan_t* const o)
+{
+	if (!tune(TUNE_MUL_PLANES) || (flags & CCV_NNC_ACCUMULATE_OUTPUT)) return false;
+	memset(o, 0, sizeof(*o));
+	if (cmd.cmd == CCV_NNC_MUL_FORWARD) {
+		if (input_size < 2 || output_size < 1 || !inputs[0] || !inputs[1] || !outputs[0]) return false;
+		if (mp_pair(inputs[0], inputs[1], o)) o->first = 0;
+		else if (mp_pair(inputs[1], inputs[0], o)) o->first = 1;
+		else return false;
+		o->out = outputs[0];
+		return mp_dense(o->out, o->dt, o->big->info.format) && mp_same_dims(o->out, o->big) && aligned16(o->out->data.u8);
+	}
+	if (cmd.cmd != CCV_NNC_MUL_BACKWARD || input_size < 3 || !inputs[0] || !inputs[1] || !inputs[2]) return false;
+	if (mp_pair(inputs[1], inputs[2], o)) o->first = 0;
+	else if (mp_pair(inputs[2], inputs[1], o)) o->first = 1;
+	else return false;
+	o->g = inputs[0];
+	ccv_nnc_tensor_t* const da = output_size > 0 ? outputs[0] : 0;
+	ccv_nnc_tensor_t* const db = output_size > 1 ? outputs[1] : 0;
+	o->dbig = o->first ? db : da;
+	o->dsmall = o->first ? da : db;
+	if (!o->dbig && !o->dsmall) return false;
+	const int format = o->big->info.format;
+	if (!mp_dense(o->g, o->dt, format) || !mp_same_dims(o->g, o->big) || !aligned16(o->g->data.u8)) return false;
+	if (o->dbig && (!mp_dense(o->dbig, o->dt, format) || !mp_same_dims(o->dbig, o->big) || !aligned16(o->dbig->data.u8))) return false;
+	if (o->dsmall && (!mp_dense(o->dsmall, o->dt, format) || !mp_same_dims(o->dsmall, o->small))) return false;
+	return true;
+}
+template <class T>
+static int mul_planes_run(const mul_plan_t& o, const float p, ccv_nnc_stream_context_t* ctx)
+{
+	if (!o.g) return mul_planes_map<T>("mul_planes_fwd", o.m, (const T*)o.big->data.u8, (const T*)o.small->data.u8, (T*)o.out->data.u8, p, o.first, ctx);
+	return mul_planes_back<T>(o.m, (const T*)o.g->data.u8, (const T*)o.big->data.u8, (const T*)o.small->data.u8, o.dbig ? (T*)o.dbig->data.u8 : (T*)0, o.dsmall ? (T*)o.dsmall->data.u8 : (T*)0, p, ctx);
+}
+
 static int _mul_forw(EXEC_ARGS)
 {
+	mul_plan_t mp;
+	if (mul_planes_plan(cmd, flags, inputs, input_size, outputs, output_size, &mp)) return mp.dt == CCV_16F ? mul_planes_run<half_t>(mp, cmd.info.blas.a[0], stream_context) : mul_planes_run<float>(mp, cmd.info.blas.a[0], stream_context);
 	if (input_size < 1 || output_size < 1 || !inputs[0] || !outputs[0] || !f32(inputs[0])) return CCV_NNC_EXEC_INVALID;
 	const ccv_nnc_tensor_t* b = input_size > 1 ? inputs[1] : 0;
 	if (!b) { FScale f; f.p = cmd.info.blas.a[0]; return bcast_map(f, inputs[0], 0, outputs[0], stream_context); }
@@ -263,6 +332,8 @@ static int _mul_forw(EXEC_ARGS)
 // inputs (g, a, b), outputs (da, db): da = p * g * b, db = p * g * a (reduced over broadcast axes); g NULL = ones
 static int _mul_back(EXEC_ARGS)
 {
+	mul_plan_t mp;
+	if (mul_planes_plan(cmd, flags, inputs, input_size, outputs, output_size, &mp)) return mp.dt == CCV_16F ? mul_planes_run<half_t>(mp, cmd.info.blas.a[0], stream_context) : mul_planes_run<float>(mp, cmd.info.blas.a[0], stream_context);
 	if (input_size < 3) return CCV_NNC_EXEC_INVALID;
 	const ccv_nnc_tensor_t* g = inputs[0];
 	const float p = cmd.info.blas.a[0];
@@ -588,6 +659,14 @@ static int _argmax_forw(EXEC_ARGS) { return argext<true>(cmd, inputs, input_size
 static int _argmin_forw(EXEC_ARGS) { return argext<false>(cmd, inputs, input_size, outputs, output_size, stream_context); }
 
 } // namespace
+
+namespace nnc {
+bool mul_planes_applies(const ccv_nnc_cmd_t cmd, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
+{
+	mul_plan_t mp;
+	return mul_planes_plan(cmd, flags, inputs, input_size, outputs, output_size, &mp);
+}
+} // namespace nnc
 
 
 #define NNC_REG(CMD, BACKEND, FORMATS, DATATYPES, MEMORY, EXEC) \

@@ -537,31 +537,95 @@ __host__ __device__ __forceinline__ unsigned mix32(unsigned x)
 }
 // `tick`: null, or (inside a captured step, device_rt.cpp "HIP-graph capture") the word the graph's first node increments -- the seed the host drew while the
 // step was being recorded is a kernel argument and would repeat with every replay
-__global__ void __launch_bounds__(EW_THREADS) dropout_forw_kernel(const float* a, float* b, unsigned char* mask, const size_t n, const unsigned seed0, const unsigned* tick, const float p, const float inv_p)
+// T = float or _Float16 (half_stage.cpp hands a and b over as halves; the mask stays the byte buffer it is): the draw depends on the seed and the element index
+// alone, so both element types -- and the 16-byte and the scalar form -- draw the same mask.  A lane takes 16 bytes of a (4 floats / 8 halves) and stores as many
+// mask bytes in one access; nv = whole vectors (0 when a base is not aligned for them), the scalar loop takes the rest.
+__device__ __forceinline__ int dropout_draw(const size_t i, const unsigned seed, const float p)
 {
+	const unsigned r = mix32(mix32((unsigned)i ^ seed) + (unsigned)(i >> 32) + 0x9e3779b9U);
+	return (float)(r >> 8) * (1.f / 16777216.f) <= p;
+}
+template <class T> struct mask_pack { typedef unsigned char type __attribute__((ext_vector_type(16 / sizeof(T)))); };
+template <class T>
+__global__ void __launch_bounds__(EW_THREADS) dropout_forw_kernel(const T* a, T* b, unsigned char* mask, const size_t nv, const size_t n, const unsigned seed0, const unsigned* tick, const float p, const float inv_p)
+{
+	constexpr int W = 16 / sizeof(T);
+	typedef typename pack16<T>::type V;
+	typedef typename mask_pack<T>::type M;
 	const unsigned seed = tick ? seed0 + 0x9e3779b9U * tick[0] : seed0;
-	const size_t stride = (size_t)gridDim.x * blockDim.x;
-	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-		const unsigned r = mix32(mix32((unsigned)i ^ seed) + (unsigned)(i >> 32) + 0x9e3779b9U);
-		const int drop = (float)(r >> 8) * (1.f / 16777216.f) <= p;
+	const size_t stride = (size_t)gridDim.x * blockDim.x, tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	for (size_t v = tid; v < nv; v += stride) {
+		const V x = ((const V*)a)[v];
+		V r;
+		M m;
+#pragma unroll
+		for (int e = 0; e < W; e++) {
+			const int drop = dropout_draw(v * W + e, seed, p);
+			m[e] = (unsigned char)drop;
+			r[e] = drop ? (T)0.f : (T)f32_rounded((float)x[e] * inv_p);
+		}
+		((M*)mask)[v] = m;
+		((V*)b)[v] = r;
+	}
+	for (size_t i = nv * W + tid; i < n; i += stride) {
+		const int drop = dropout_draw(i, seed, p);
 		mask[i] = (unsigned char)drop;
-		b[i] = drop ? 0.f : a[i] * inv_p;
+		b[i] = drop ? (T)0.f : (T)f32_rounded((float)a[i] * inv_p);
 	}
 }
-__global__ void __launch_bounds__(EW_THREADS) dropout_back_kernel(const float* g, float* h, const unsigned char* mask, const size_t n, const float inv_p)
+template <class T>
+__global__ void __launch_bounds__(EW_THREADS) dropout_back_kernel(const T* g, T* h, const unsigned char* mask, const size_t nv, const size_t n, const float inv_p)
 {
-	const size_t stride = (size_t)gridDim.x * blockDim.x;
-	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) h[i] = mask[i] ? 0.f : g[i] * inv_p;
+	constexpr int W = 16 / sizeof(T);
+	typedef typename pack16<T>::type V;
+	typedef typename mask_pack<T>::type M;
+	const size_t stride = (size_t)gridDim.x * blockDim.x, tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	for (size_t v = tid; v < nv; v += stride) {
+		const V x = ((const V*)g)[v];
+		const M m = ((const M*)mask)[v];
+		V r;
+#pragma unroll
+		for (int e = 0; e < W; e++) r[e] = m[e] ? (T)0.f : (T)f32_rounded((float)x[e] * inv_p);
+		((V*)h)[v] = r;
+	}
+	for (size_t i = nv * W + tid; i < n; i += stride) h[i] = mask[i] ? (T)0.f : (T)f32_rounded((float)g[i] * inv_p);
 }
 __global__ void __launch_bounds__(64) dropout_decide_kernel(int* decision, const unsigned seed0, const unsigned* tick, const float p)
 { // the whole-tensor decision of a captured step: made on the device from the replay's tick (outside a capture the host decides and copies the word)
 	if (threadIdx.x == 0 && blockIdx.x == 0) decision[0] = (float)(mix32(seed0 + 0x9e3779b9U * tick[0]) >> 8) * (1.f / 16777216.f) <= p;
 }
-__global__ void __launch_bounds__(EW_THREADS) dropout_entire_kernel(const float* a, float* b, const int* decision, const size_t n, const float inv_p)
+template <class T>
+__global__ void __launch_bounds__(EW_THREADS) dropout_entire_kernel(const T* a, T* b, const int* decision, const size_t nv, const size_t n, const float inv_p)
 {
+	constexpr int W = 16 / sizeof(T);
+	typedef typename pack16<T>::type V;
 	const int drop = decision[0];
-	const size_t stride = (size_t)gridDim.x * blockDim.x;
-	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) b[i] = drop ? 0.f : a[i] * inv_p;
+	const size_t stride = (size_t)gridDim.x * blockDim.x, tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	for (size_t v = tid; v < nv; v += stride) {
+		const V x = ((const V*)a)[v];
+		V r;
+#pragma unroll
+		for (int e = 0; e < W; e++) r[e] = drop ? (T)0.f : (T)f32_rounded((float)x[e] * inv_p);
+		((V*)b)[v] = r;
+	}
+	for (size_t i = nv * W + tid; i < n; i += stride) b[i] = drop ? (T)0.f : (T)f32_rounded((float)a[i] * inv_p);
+}
+// the three launches, on the tensors' own element type; `mask` null: the whole-tensor form reading `decision`
+template <class T>
+static void dropout_launch(const int back, const void* in, void* out, unsigned char* mask, const int* decision, const size_t n, const unsigned seed, const unsigned* tick, const float p, const float inv_p, hipStream_t stream)
+{
+	constexpr int W = 16 / sizeof(T);
+	const bool vec = aligned16(in) && aligned16(out) && (!mask || ((uintptr_t)mask & (W - 1)) == 0);
+	const size_t nv = vec ? n / W : 0;
+	const dim3 grid(grid_for(vec ? nv + (W - 1) : n, EW_THREADS)), block(EW_THREADS);
+	if (!mask) hipLaunchKernelGGL(HIP_KERNEL_NAME(dropout_entire_kernel<T>), grid, block, 0, stream, (const T*)in, (T*)out, decision, nv, n, inv_p);
+	else if (back) hipLaunchKernelGGL(HIP_KERNEL_NAME(dropout_back_kernel<T>), grid, block, 0, stream, (const T*)in, (T*)out, (const unsigned char*)mask, nv, n, inv_p);
+	else hipLaunchKernelGGL(HIP_KERNEL_NAME(dropout_forw_kernel<T>), grid, block, 0, stream, (const T*)in, (T*)out, mask, nv, n, seed, tick, p, inv_p);
+}
+static void dropout_launch_any(const int dt, const int back, const void* in, void* out, unsigned char* mask, const int* decision, const size_t n, const unsigned seed, const unsigned* tick, const float p, const float inv_p, hipStream_t stream)
+{
+	if (dt == CCV_16F) dropout_launch<half_t>(back, in, out, mask, decision, n, seed, tick, p, inv_p, stream);
+	else dropout_launch<float>(back, in, out, mask, decision, n, seed, tick, p, inv_p, stream);
 }
 
 // The host's per-stream generator when the reference host is linked in (lib/nnc/ccv_nnc_stream.c:262), else a process counter.
@@ -577,7 +641,8 @@ static int _dropout_forw(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, con
 {
 	if (input_size < 1 || output_size < 2 || !inputs[0] || !outputs[0] || !outputs[1]) return CCV_NNC_EXEC_INVALID;
 	const ccv_nnc_tensor_t* a = inputs[0];
-	if (CCV_GET_DATA_TYPE(a->info.datatype) != CCV_32F || !tensor_contiguous(a) || !tensor_contiguous(outputs[0])) return CCV_NNC_EXEC_INVALID;
+	const int dt = CCV_GET_DATA_TYPE(a->info.datatype); // CCV_16F: only when half_stage.cpp handed a and b over as halves
+	if ((dt != CCV_32F && dt != CCV_16F) || CCV_GET_DATA_TYPE(outputs[0]->info.datatype) != dt || !tensor_contiguous(a) || !tensor_contiguous(outputs[0])) return CCV_NNC_EXEC_INVALID;
 	const size_t n = tensor_count(a->info);
 	if (tensor_count(outputs[0]->info) != n) return CCV_NNC_EXEC_INVALID;
 	const float p = cmd.info.dropout.p, inv_p = 1.f / (1.f - p);
@@ -591,10 +656,10 @@ static int _dropout_forw(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, con
 		const int drop = (float)(mix32(seed) >> 8) * (1.f / 16777216.f) <= p;
 		if (tick) hipLaunchKernelGGL(dropout_decide_kernel, dim3(1), dim3(64), 0, stream, outputs[1]->data.i32, seed, tick, p); // (a captured copy node would re-read this stack word at every replay)
 		else HIP_ENFORCE(hipMemcpyAsync(outputs[1]->data.u8, &drop, sizeof(int), hipMemcpyHostToDevice, stream)); // pageable source: copied before return
-		hipLaunchKernelGGL(dropout_entire_kernel, dim3(grid_for(n, EW_THREADS)), dim3(EW_THREADS), 0, stream, (const float*)a->data.f32, outputs[0]->data.f32, (const int*)outputs[1]->data.i32, n, inv_p);
+		dropout_launch_any(dt, 0, a->data.u8, outputs[0]->data.u8, 0, (const int*)outputs[1]->data.i32, n, seed, tick, p, inv_p, stream);
 	} else {
 		if (mask_bytes < n) return CCV_NNC_EXEC_INVALID;
-		hipLaunchKernelGGL(dropout_forw_kernel, dim3(grid_for(n, EW_THREADS)), dim3(EW_THREADS), 0, stream, (const float*)a->data.f32, outputs[0]->data.f32, outputs[1]->data.u8, n, seed, tick, p, inv_p);
+		dropout_launch_any(dt, 0, a->data.u8, outputs[0]->data.u8, outputs[1]->data.u8, 0, n, seed, tick, p, inv_p, stream);
 	}
 	HIP_ENFORCE(hipGetLastError());
 	return CCV_NNC_EXEC_SUCCESS;
@@ -603,14 +668,15 @@ static int _dropout_back(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, con
 { // inputs (g, _, _, _, mask), output h   (dropout_cpu_ref.c:149-)
 	if (input_size < 5 || output_size < 1 || !inputs[0] || !inputs[4] || !outputs[0]) return CCV_NNC_EXEC_INVALID;
 	const ccv_nnc_tensor_t* g = inputs[0];
-	if (CCV_GET_DATA_TYPE(g->info.datatype) != CCV_32F || !tensor_contiguous(g) || !tensor_contiguous(outputs[0])) return CCV_NNC_EXEC_INVALID;
+	const int dt = CCV_GET_DATA_TYPE(g->info.datatype);
+	if ((dt != CCV_32F && dt != CCV_16F) || CCV_GET_DATA_TYPE(outputs[0]->info.datatype) != dt || !tensor_contiguous(g) || !tensor_contiguous(outputs[0])) return CCV_NNC_EXEC_INVALID;
 	const size_t n = tensor_count(g->info);
 	if (tensor_count(outputs[0]->info) != n) return CCV_NNC_EXEC_INVALID;
 	if (n == 0) return CCV_NNC_EXEC_SUCCESS;
 	const float inv_p = 1.f / (1.f - cmd.info.dropout.p);
 	hipStream_t stream = stream_of(stream_context);
-	if (cmd.info.dropout.entirety) hipLaunchKernelGGL(dropout_entire_kernel, dim3(grid_for(n, EW_THREADS)), dim3(EW_THREADS), 0, stream, (const float*)g->data.f32, outputs[0]->data.f32, (const int*)inputs[4]->data.i32, n, inv_p);
-	else hipLaunchKernelGGL(dropout_back_kernel, dim3(grid_for(n, EW_THREADS)), dim3(EW_THREADS), 0, stream, (const float*)g->data.f32, outputs[0]->data.f32, (const unsigned char*)inputs[4]->data.u8, n, inv_p);
+	if (cmd.info.dropout.entirety) dropout_launch_any(dt, 1, g->data.u8, outputs[0]->data.u8, 0, (const int*)inputs[4]->data.i32, n, 0, 0, 0.f, inv_p, stream);
+	else dropout_launch_any(dt, 1, g->data.u8, outputs[0]->data.u8, inputs[4]->data.u8, 0, n, 0, 0, 0.f, inv_p, stream);
 	HIP_ENFORCE(hipGetLastError());
 	return CCV_NNC_EXEC_SUCCESS;
 }

@@ -71,6 +71,18 @@ static inline bool tensor_contiguous(const ccv_nnc_tensor_t* t)
 	return true;
 }
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// An fp32 result stored as a half is rounded TWICE, to fp32 by the arithmetic and to half by the store: that is what an fp32 kernel followed by a conversion
+// gives, and what the half-precision rows are compared with bit for bit.  Left alone, the gfx950 compiler merges a final fp32 multiply and the conversion
+// into one v_fma_mixlo_f16, which rounds the exact product once, and the last bit differs now and then.  Canonicalizing an arithmetic result is no
+// instruction, and keeps the two roundings apart.  (Host builds of the kernels have no such instruction to merge into.)
+__device__ __forceinline__ float f32_rounded(const float v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	return __builtin_elementwise_canonicalize(v);
+#else
+	return v;
+#endif
+}
 
 // A 4-d (N, H, W, C) logical view of an image-like tensor in either layout, with element strides.
 struct Image4 {
@@ -260,6 +272,8 @@ enum {
 	TUNE_GEMM_BATCH_XCD,    // batched contractions without split-K (a 1 x 1 convolution on NCHW tensors: one matrix product per image) launch ONE grid dimension over (entry, tile) and give every batch entry to one XCD: the tiles of an entry meet in ONE L2, so its B operand -- the image's planes, which every row block of the output reads -- leaves HBM once, not once per XCD (1); 0 = entries on grid z, tiles dealt round-robin over the XCDs (rounds 1 - 5)
 	TUNE_CONV_BACK_SHARE,   // a backward convolution that computes both gradients reads a tensor ONCE where two of its kernels read the same one: bit 0 = the output gradient's two Winograd transforms (data gradient V, filter gradient W, bias sums) in one kernel, bit 1 = the fused data gradient's ReLU mask bits written by the filter gradient's input transform; 0 = the separate kernels (rounds 1 - 6; the results are bit for bit the same)
 	TUNE_CONV_DEPTHWISE,    // depthwise convolutions (groups == channels == filters, dense tensors of one type and one format) on the direct stencil kernels of conv_depthwise.h (1), or as `groups` one-column implicit GEMMs (0)
+	TUNE_ACT_HALF_NATIVE,   // the activations (sigmoid, tanh, GELU, swish, leaky ReLU; forward and backward) and dropout read and write CCV_16F tensors as halves themselves (1), or run on fp32 images of them (0)
+	TUNE_MUL_PLANES,        // MUL of a dense 4-d activation tensor by a per-(image, channel) vector (squeeze-excite), forward and backward, fp32 and half, on the plane-scale kernels of mul_planes.h (1), or the generic broadcast map / reduce kernels (0)
 	TUNE_COUNT
 };
 static_assert(TUNE_GRID_WG_PER_CU == 3, "grid_for() above names this key by value");
@@ -306,6 +320,9 @@ static int half_staged(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const
 	return half_staged_exec([](void*, const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const ctx) { return F(cmd, hint, flags, inputs, input_size, outputs, output_size, ctx); }, 0, cmd, hint, flags, inputs, input_size, outputs, output_size, ctx);
 }
 #define NNC_HALF_STAGED(registry, EXEC) do { if (((registry)->tensor_datatypes & CCV_32F) && !((registry)->tensor_datatypes & CCV_16F)) { /* rows that list CCV_16F themselves handle it natively */ (registry)->tensor_datatypes |= CCV_16F; (registry)->exec = nnc::half_staged<EXEC>; } } while (0)
+// cmd_bcast.cpp: is this MUL_FORWARD / MUL_BACKWARD command one the plane-scale kernels (mul_planes.h) take?  The row asks before it routes; half_stage.cpp asks
+// before it leaves the command's half tensors in their own memory -- one answer for both.
+bool mul_planes_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size);
 bool any_half_tensor(ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size);
 int half_to_float(const void* in, float* out, size_t n, ccv_nnc_stream_context_t* ctx);
 int float_to_half(const float* in, void* out, size_t n, ccv_nnc_stream_context_t* ctx);

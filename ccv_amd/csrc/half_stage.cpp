@@ -145,7 +145,7 @@ void warn_refused(const uint32_t cmd, const int ret)
 }
 
 // Rows whose kernels read and write their LARGE tensors in half precision themselves (loads / stores of halves, fp32 arithmetic:
-// cmd_ew.cpp, cmd_norm.cpp, cmd_pool.cpp).  Bit i of `in` / `out` = that input / output stays in its own memory when every tensor
+// cmd_ew.cpp, cmd_norm.cpp, cmd_pool.cpp, cmd_act_opt.cpp, cmd_bcast.cpp's plane-scale MUL).  Bit i of `in` / `out` = that input / output stays in its own memory when every tensor
 // named by the masks is a dense CCV_16F tensor; the row's small tensors (batch-norm statistics, ...) still get fp32 images.
 static long g_half_staged = 0, g_half_native = 0; // nnc_mi355x_debug_half_counts (test hook; not synchronised: counts, not control)
 // NNC_MI355X_HALF_STATS=1: one line per command at unload -- which rows of a run went through fp32 images of their half tensors (and how many tensors)
@@ -165,7 +165,12 @@ static void half_stats_note(const uint32_t cmd, const int tensors)
 	for (int i = 0; i < g_half_stats.n; i++) if (g_half_stats.row[i].cmd == cmd) { g_half_stats.row[i].calls++; g_half_stats.row[i].tensors += tensors; return; }
 	if (g_half_stats.n < 64) { g_half_stats.row[g_half_stats.n].cmd = cmd; g_half_stats.row[g_half_stats.n].calls = 1; g_half_stats.row[g_half_stats.n].tensors = tensors; g_half_stats.n++; }
 }
-struct native_half_t { uint32_t cmd; unsigned in, out; };
+// `when`: null, or the row is native only for the commands it accepts (asked after the masks have matched: every tensor they name is a dense CCV_16F one)
+typedef bool (*native_when_f)(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size);
+struct native_half_t { uint32_t cmd; unsigned in, out; native_when_f when; };
+static bool act_native(const ccv_nnc_cmd_t, int, ccv_nnc_tensor_t* const*, int, ccv_nnc_tensor_t* const*, int) { return tune(TUNE_ACT_HALF_NATIVE) != 0; }
+// the backward commands without g (ones) keep their fp32 kernels (cmd_act_opt.cpp)
+static bool act_back_native(const ccv_nnc_cmd_t, int, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const*, int) { return tune(TUNE_ACT_HALF_NATIVE) != 0 && input_size > 0 && inputs[0]; }
 static const native_half_t g_native_half[] = {
 	{ CCV_NNC_RELU_FORWARD, 1u << 0, 1u << 0 },
 	{ CCV_NNC_RELU_BACKWARD, (1u << 0) | (1u << 2), 1u << 0 },            // g, (a unused), b -> h
@@ -180,10 +185,27 @@ static const native_half_t g_native_half[] = {
 	{ CCV_NNC_SGD_FORWARD, (1u << 0) | (1u << 1) | (1u << 2), (1u << 0) | (1u << 1) }, // g, a, m -> b, n
 	{ CCV_NNC_SOFTMAX_CROSSENTROPY_FORWARD, 1u << 0, 1u << 1 },           // logits -> softmax (labels and the loss: fp32 images, a value per row)
 	{ CCV_NNC_SOFTMAX_CROSSENTROPY_BACKWARD, 1u << 5, 1u << 0 },          // softmax -> h
+	// cmd_act_opt.cpp: a -> b;  g, (a unused), b -> h  or  g, a -> h
+	{ CCV_NNC_SIGMOID_FORWARD, 1u << 0, 1u << 0, act_native },
+	{ CCV_NNC_SIGMOID_BACKWARD, (1u << 0) | (1u << 2), 1u << 0, act_back_native },
+	{ CCV_NNC_TANH_FORWARD, 1u << 0, 1u << 0, act_native },
+	{ CCV_NNC_TANH_BACKWARD, (1u << 0) | (1u << 2), 1u << 0, act_back_native },
+	{ CCV_NNC_GELU_FORWARD, 1u << 0, 1u << 0, act_native },
+	{ CCV_NNC_GELU_BACKWARD, (1u << 0) | (1u << 1), 1u << 0, act_back_native },
+	{ CCV_NNC_SWISH_FORWARD, 1u << 0, 1u << 0, act_native },
+	{ CCV_NNC_SWISH_BACKWARD, (1u << 0) | (1u << 1), 1u << 0, act_back_native },
+	{ CCV_NNC_LEAKY_RELU_FORWARD, 1u << 0, 1u << 0, act_native },
+	{ CCV_NNC_LEAKY_RELU_BACKWARD, (1u << 0) | (1u << 2), 1u << 0, act_back_native },
+	{ CCV_NNC_DROPOUT_FORWARD, 1u << 0, 1u << 0, act_native },            // a -> b (the mask is opaque, below)
+	{ CCV_NNC_DROPOUT_BACKWARD, 1u << 0, 1u << 0, act_native },           // g -> h
+	// cmd_bcast.cpp: only the squeeze-excite pattern of mul_planes.h; every other MUL runs on fp32 images
+	{ CCV_NNC_MUL_FORWARD, (1u << 0) | (1u << 1), 1u << 0, mul_planes_applies },            // a, b -> c
+	{ CCV_NNC_MUL_BACKWARD, (1u << 0) | (1u << 1) | (1u << 2), (1u << 0) | (1u << 1), mul_planes_applies }, // g, a, b -> da, db
 };
-static const native_half_t* native_half_row(const uint32_t cmd, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
+static const native_half_t* native_half_row(const ccv_nnc_cmd_t command, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
 {
 	if (flags & CCV_NNC_ACCUMULATE_OUTPUT) return 0;
+	const uint32_t cmd = command.cmd;
 	for (const native_half_t& r : g_native_half) {
 		if (r.cmd != cmd) continue;
 		int seen = 0;
@@ -191,7 +213,7 @@ static const native_half_t* native_half_row(const uint32_t cmd, const int flags,
 			if (((r.in >> i) & 1) && inputs[i]) { if (CCV_GET_DATA_TYPE(inputs[i]->info.datatype) != CCV_16F || CCV_IS_TENSOR_VIEW(inputs[i])) return 0; seen++; }
 		for (int i = 0; i < output_size && i < 32; i++)
 			if (((r.out >> i) & 1) && outputs[i]) { if (CCV_GET_DATA_TYPE(outputs[i]->info.datatype) != CCV_16F || CCV_IS_TENSOR_VIEW(outputs[i])) return 0; seen++; }
-		return seen ? &r : 0;
+		return seen && (!r.when || r.when(command, flags, inputs, input_size, outputs, output_size)) ? &r : 0;
 	}
 	return 0;
 }
@@ -237,7 +259,7 @@ int half_staged_exec(const nnc_exec_user_f inner, void* const user, const ccv_nn
 	// one spans at least the bytes fp32 planes need and the kernels keep their tape (gates, tanh(c), cell states, dropout scales) in fp32 inside it -- nothing is
 	// rounded to half between the forward and the backward command, no cell state can overflow the half range, and the space is not converted twice per call
 	const int opaque_in = cmd.cmd == CCV_NNC_DROPOUT_BACKWARD ? 4 : (cmd.cmd == CCV_NNC_LSTM_BACKWARD ? 12 : -1), opaque_out = cmd.cmd == CCV_NNC_DROPOUT_FORWARD ? 1 : (cmd.cmd == CCV_NNC_LSTM_FORWARD ? 3 : -1);
-	const native_half_t* const native = native_half_row(cmd.cmd, flags, inputs, input_size, outputs, output_size);
+	const native_half_t* const native = native_half_row(cmd, flags, inputs, input_size, outputs, output_size);
 	for (int i = 0; i < input_size; i++) { if (i == opaque_in || (native && i < 32 && ((native->in >> i) & 1))) which[i] = -1; else visit(inputs[i], false, i); }
 	for (int i = 0; i < output_size; i++) { if (i == opaque_out || (native && i < 32 && ((native->out >> i) & 1))) which[input_size + i] = -1; else visit(outputs[i], true, input_size + i); }
 	for (int i = 0; i < nst; i++) total += (st[i].span * sizeof(float) + 255) & ~(size_t)255;
