@@ -1,5 +1,5 @@
-// Activations, plain softmax and the Adam / AdamW / RMSProp update on gfx950 -- the element-wise rows the reference's other
-// trainers need beside SGD.  All HBM-bound: grid-stride, 16 bytes per lane when aligned.  The five activation families run
+// Activations, plain softmax and the Adam / AdamW / RMSProp / LAMB update on gfx950 -- the element-wise rows the reference's other
+// trainers need beside SGD.  All HBM-bound: 16 bytes per lane when aligned; the activations grid-stride, the optimizers (optim.h) a tile per workgroup.  The five activation families run
 // CCV_16F tensors as halves themselves (act_map_kernel; half_stage.cpp g_native_half, tunable ACT_HALF_NATIVE).
 // Oracle semantics (CPU reference, fp32 storage, arithmetic promoted to double there; float here, within 1e-6):
 //   sigmoid     lib/nnc/cmd/sigmoid/ccv_nnc_sigmoid_cpu_ref.c:13-66        b = 1/(1+e^-a);  h = g b (1-b)      (g may be absent: ones)
@@ -13,6 +13,7 @@
 //   rmsprop     lib/nnc/cmd/rmsprop/ccv_nnc_rmsprop_cpu_ref.c:16-108       inputs (g, a, m, v) -> (b, n, u)
 //   lamb        lib/nnc/cmd/lamb/ccv_nnc_lamb_cpu_ref.c:16-140             Adam-style update scaled per TENSOR by |w| / |update| (norms in double)
 #include "common.h"
+#include "optim.h"
 
 using namespace nnc;
 
@@ -100,7 +101,7 @@ static bool same_count(const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* b) { r
 static bool dense_f32(const ccv_nnc_tensor_t* t) { return t && tensor_contiguous(t) && CCV_GET_DATA_TYPE(t->info.datatype) == CCV_32F; }
 // dense, and of datatype dt
 static bool dense_of(const ccv_nnc_tensor_t* t, const int dt) { return t && tensor_contiguous(t) && CCV_GET_DATA_TYPE(t->info.datatype) == dt; }
-// CCV_32F or CCV_16F (the latter only ever arrives when half_stage.cpp's table handed ALL of the command's tensors over as halves), else 0
+// CCV_32F or CCV_16F (the latter only ever arrives through a native row of half_stage.cpp's table), else 0
 static int float_type(const ccv_nnc_tensor_t* t)
 {
 	const int dt = t ? CCV_GET_DATA_TYPE(t->info.datatype) : 0;
@@ -216,155 +217,96 @@ static int _softmax_back(EXEC_ARGS)
 	return CCV_NNC_EXEC_SUCCESS;
 }
 
-// ---- optimizers: one pass over (g, a, m, v[, vm]) -> (b, n, u[, um]); 7-9 |p| bytes -------------------------------------------
-struct AdamP { float scale, beta1, beta2, decay, epsilon, rate_corr1, inv_corr2, rate_decay; int decoupled, amsgrad; };
-__global__ void __launch_bounds__(EW_THREADS) adam_kernel(const AdamP p, const float* g, const float* a, const float* m, const float* v, const float* vm, float* b, float* nm, float* u, float* um, const size_t n)
+// ---- optimizers: one pass over (g, a, m, v[, vm]) -> (b, n, u[, um]); the kernels and the arithmetic are optim.h's --------------------------------
+// g is CCV_32F or CCV_16F; the parameter and state tensors share one of the two types (what the reference's GPU kernels dispatch on).  CCV_16F tensors arrive
+// here only through half_stage.cpp's native rows (tunable OPT_HALF_NATIVE); without them every tensor is an fp32 one or an fp32 image.
+// -> 0 and the two types, or the code to return: dense tensors of one element count, g of *tg, the others of *tp
+static int opt_tensors(ccv_nnc_tensor_t* const* const inputs, const int nin, ccv_nnc_tensor_t* const* const outputs, const int nout, int* const tg, int* const tp, size_t* const n)
 {
-	const size_t stride = (size_t)gridDim.x * blockDim.x;
-	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-		const float av = a[i];
-		float grad = p.scale * g[i];
-		if (!p.decoupled) grad += p.decay * av;
-		const float mom = p.beta1 * m[i] + (1.f - p.beta1) * grad;
-		const float vel = p.beta2 * v[i] + (1.f - p.beta2) * grad * grad;
-		nm[i] = mom;
-		u[i] = vel;
-		float denom;
-		if (p.amsgrad) {
-			const float vel_max_hat = fmaxf(vm[i], vel * p.inv_corr2);
-			um[i] = vel_max_hat;
-			denom = sqrtf(vel_max_hat) + p.epsilon;
-		} else
-			denom = sqrtf(vel * p.inv_corr2) + p.epsilon;
-		const float base = p.decoupled ? av - p.rate_decay * av : av;
-		b[i] = base - (mom * p.rate_corr1) / denom;
-	}
+	*tg = float_type(inputs[0]);
+	*tp = float_type(inputs[1]);
+	if (!*tg || !*tp || !dense_of(inputs[0], *tg)) return CCV_NNC_EXEC_INVALID;
+	for (int i = 1; i < nin; i++) if (!dense_of(inputs[i], *tp)) return CCV_NNC_EXEC_INVALID;
+	for (int i = 0; i < nout; i++) if (!dense_of(outputs[i], *tp)) return CCV_NNC_EXEC_INVALID;
+	*n = tensor_count(inputs[1]->info);
+	for (int i = 0; i < nin; i++) if (tensor_count(inputs[i]->info) != *n) return CCV_NNC_EXEC_INVALID;
+	for (int i = 0; i < nout; i++) if (tensor_count(outputs[i]->info) != *n) return CCV_NNC_EXEC_INVALID;
+	return 0;
 }
-static int adam_exec(const ccv_nnc_cmd_t& cmd, const int decoupled, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const ctx)
+// CALL<TG, TP>() for the pair of element types
+#define OPT_DISPATCH(tg, tp, CALL) ((tg) == CCV_16F ? ((tp) == CCV_16F ? CALL(optim::half_t, optim::half_t) : CALL(optim::half_t, float)) : ((tp) == CCV_16F ? CALL(float, optim::half_t) : CALL(float, float)))
+
+static optim::opt_ptrs_t opt_ptrs(ccv_nnc_tensor_t* const* const inputs, const int nin, ccv_nnc_tensor_t* const* const outputs, const int nout)
 {
-	if (input_size < 4 || output_size < 3) return CCV_NNC_EXEC_INVALID;
-	for (int i = 0; i < 4; i++) if (!dense_f32(inputs[i])) return CCV_NNC_EXEC_INVALID;
-	for (int i = 0; i < 3; i++) if (!dense_f32(outputs[i])) return CCV_NNC_EXEC_INVALID;
-	const ccv_nnc_tensor_t* vm = input_size >= 5 ? inputs[4] : 0;
-	ccv_nnc_tensor_t* um = output_size >= 4 ? outputs[3] : 0;
-	const int ams = cmd.info.adam.amsgrad && vm && um;
-	if (ams && (!dense_f32(vm) || !dense_f32(um))) return CCV_NNC_EXEC_INVALID;
-	const size_t n = tensor_count(inputs[1]->info);
-	for (int i = 0; i < 4; i++) if (tensor_count(inputs[i]->info) != n) return CCV_NNC_EXEC_INVALID;
-	for (int i = 0; i < 3; i++) if (tensor_count(outputs[i]->info) != n) return CCV_NNC_EXEC_INVALID;
-	if (n == 0) return CCV_NNC_EXEC_SUCCESS;
-	AdamP p;
+	optim::opt_ptrs_t p = {};
+	for (int i = 0; i < nin; i++) p.in[i] = inputs[i]->data.u8;
+	for (int i = 0; i < nout; i++) p.out[i] = outputs[i]->data.u8;
+	return p;
+}
+template <bool DECOUPLED, bool AMS>
+static int adam_run(const ccv_nnc_cmd_t& cmd, const int tg, const int tp, const optim::opt_ptrs_t& ptrs, const size_t n, ccv_nnc_stream_context_t* const ctx)
+{
+	optim::AdamOp<DECOUPLED, AMS> p;
 	p.scale = cmd.info.adam.scale; p.beta1 = cmd.info.adam.beta1; p.beta2 = cmd.info.adam.beta2; p.decay = cmd.info.adam.decay; p.epsilon = cmd.info.adam.epsilon;
 	p.rate_corr1 = cmd.info.adam.rate / (1 - powf(p.beta1, (float)cmd.info.adam.step));
 	p.inv_corr2 = 1.f / (1 - powf(p.beta2, (float)cmd.info.adam.step));
 	p.rate_decay = cmd.info.adam.rate * p.decay;
-	p.decoupled = decoupled; p.amsgrad = ams;
-	hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n, EW_THREADS)), dim3(EW_THREADS), 0, stream_of(ctx), p, (const float*)inputs[0]->data.f32, (const float*)inputs[1]->data.f32, (const float*)inputs[2]->data.f32, (const float*)inputs[3]->data.f32,
-		ams ? (const float*)vm->data.f32 : (const float*)0, outputs[0]->data.f32, outputs[1]->data.f32, outputs[2]->data.f32, ams ? um->data.f32 : (float*)0, n);
-	HIP_ENFORCE(hipGetLastError());
-	return CCV_NNC_EXEC_SUCCESS;
+	const char* const name = DECOUPLED ? "optim_adamw" : "optim_adam";
+#define ADAM_CALL(TG, TP) optim::opt_pass<optim::AdamOp<DECOUPLED, AMS>, TG, TP>(name, p, ptrs, n, ctx)
+	return OPT_DISPATCH(tg, tp, ADAM_CALL);
+#undef ADAM_CALL
+}
+static int adam_exec(const ccv_nnc_cmd_t& cmd, const int decoupled, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const ctx)
+{
+	if (input_size < 4 || output_size < 3) return CCV_NNC_EXEC_INVALID;
+	const ccv_nnc_tensor_t* vm = input_size >= 5 ? inputs[4] : 0;
+	ccv_nnc_tensor_t* um = output_size >= 4 ? outputs[3] : 0;
+	const int ams = cmd.info.adam.amsgrad && vm && um;
+	int tg, tp;
+	size_t n;
+	const int bad = opt_tensors(inputs, ams ? 5 : 4, outputs, ams ? 4 : 3, &tg, &tp, &n);
+	if (bad) return bad;
+	if (n == 0) return CCV_NNC_EXEC_SUCCESS;
+	const optim::opt_ptrs_t ptrs = opt_ptrs(inputs, ams ? 5 : 4, outputs, ams ? 4 : 3);
+	if (decoupled) return ams ? adam_run<true, true>(cmd, tg, tp, ptrs, n, ctx) : adam_run<true, false>(cmd, tg, tp, ptrs, n, ctx);
+	return ams ? adam_run<false, true>(cmd, tg, tp, ptrs, n, ctx) : adam_run<false, false>(cmd, tg, tp, ptrs, n, ctx);
 }
 static int _adam_forw(EXEC_ARGS) { return adam_exec(cmd, 0, IO); }
 static int _adamw_forw(EXEC_ARGS) { return adam_exec(cmd, 1, IO); }
 
-__global__ void __launch_bounds__(EW_THREADS) rmsprop_kernel(const float* g, const float* a, const float* m, const float* v, float* b, float* nm, float* u, const size_t n, const float rate, const float scale, const float decay, const float alpha, const float momentum, const float epsilon)
-{
-	const size_t stride = (size_t)gridDim.x * blockDim.x;
-	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-		const float av = a[i];
-		const float grad = scale * g[i] + decay * av;
-		const float vel = alpha * v[i] + (1.f - alpha) * grad * grad;
-		const float mom = momentum * m[i] + grad / (sqrtf(vel) + epsilon);
-		u[i] = vel;
-		nm[i] = mom;
-		b[i] = av - rate * mom;
-	}
-}
 static int _rmsprop_forw(EXEC_ARGS)
 {
 	if (input_size < 4 || output_size < 3) return CCV_NNC_EXEC_INVALID;
-	for (int i = 0; i < 4; i++) if (!dense_f32(inputs[i])) return CCV_NNC_EXEC_INVALID;
-	for (int i = 0; i < 3; i++) if (!dense_f32(outputs[i])) return CCV_NNC_EXEC_INVALID;
-	const size_t n = tensor_count(inputs[1]->info);
-	for (int i = 0; i < 4; i++) if (tensor_count(inputs[i]->info) != n) return CCV_NNC_EXEC_INVALID;
-	for (int i = 0; i < 3; i++) if (tensor_count(outputs[i]->info) != n) return CCV_NNC_EXEC_INVALID;
+	int tg, tp;
+	size_t n;
+	const int bad = opt_tensors(inputs, 4, outputs, 3, &tg, &tp, &n);
+	if (bad) return bad;
 	if (n == 0) return CCV_NNC_EXEC_SUCCESS;
-	hipLaunchKernelGGL(rmsprop_kernel, dim3(grid_for(n, EW_THREADS)), dim3(EW_THREADS), 0, stream_of(stream_context), (const float*)inputs[0]->data.f32, (const float*)inputs[1]->data.f32, (const float*)inputs[2]->data.f32, (const float*)inputs[3]->data.f32,
-		outputs[0]->data.f32, outputs[1]->data.f32, outputs[2]->data.f32, n, cmd.info.rmsprop.rate, cmd.info.rmsprop.scale, cmd.info.rmsprop.decay, cmd.info.rmsprop.alpha, cmd.info.rmsprop.momentum, cmd.info.rmsprop.epsilon);
-	HIP_ENFORCE(hipGetLastError());
-	return CCV_NNC_EXEC_SUCCESS;
+	const optim::RmspropOp p = { cmd.info.rmsprop.rate, cmd.info.rmsprop.scale, cmd.info.rmsprop.decay, cmd.info.rmsprop.alpha, cmd.info.rmsprop.momentum, cmd.info.rmsprop.epsilon };
+	const optim::opt_ptrs_t ptrs = opt_ptrs(inputs, 4, outputs, 3);
+#define RMSPROP_CALL(TG, TP) optim::opt_pass<optim::RmspropOp, TG, TP>("optim_rmsprop", p, ptrs, n, stream_context)
+	return OPT_DISPATCH(tg, tp, RMSPROP_CALL);
+#undef RMSPROP_CALL
 }
 
-// ---- LAMB: update = mom^ / (sqrt(vel^) + eps) + decay w; b = a - rate (|w| / |update|) update.  Three launches: the element pass writes n, u
-// and the update (workspace) and one (sum w^2, sum update^2) pair per block in double; one block folds the pairs in order into the trust
-// ratio; the last pass applies it.  Deterministic; 9 |p| bytes. -------------------------------------------------------------------------
-struct LambP { float scale, beta1, beta2, decay, epsilon, inv_corr1, inv_corr2; };
-__global__ void __launch_bounds__(EW_THREADS) lamb_update_kernel(const LambP p, const float* g, const float* a, const float* m, const float* v, float* nm, float* u, float* update, double* partial, const size_t n)
-{
-	__shared__ double red[2][4];
-	const size_t stride = (size_t)gridDim.x * blockDim.x;
-	double wn = 0, un = 0;
-	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-		const float grad = p.scale * g[i], w = a[i];
-		const float mom = p.beta1 * m[i] + (1.f - p.beta1) * grad;
-		const float vel = p.beta2 * v[i] + (1.f - p.beta2) * grad * grad;
-		nm[i] = mom;
-		u[i] = vel;
-		const float upd = (mom * p.inv_corr1) / (sqrtf(vel * p.inv_corr2) + p.epsilon) + w * p.decay;
-		update[i] = upd;
-		wn += (double)(w * w);
-		un += (double)(upd * upd);
-	}
-	for (int o = 32; o > 0; o >>= 1) { wn += __shfl_xor(wn, o); un += __shfl_xor(un, o); }
-	if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = wn; red[1][threadIdx.x >> 6] = un; }
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		partial[2 * blockIdx.x] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-		partial[2 * blockIdx.x + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-	}
-}
-__global__ void lamb_trust_kernel(const double* partial, const int blocks, const float rate, float* rate_trust)
-{
-	double wn = 0, un = 0;
-	for (int i = 0; i < blocks; i++) { wn += partial[2 * i]; un += partial[2 * i + 1]; }
-	wn = sqrt(wn); un = sqrt(un);
-	const float trust = (wn > 0 && un > 0) ? (float)(wn / un) : 1.f;
-	*rate_trust = rate * trust;
-}
-__global__ void __launch_bounds__(EW_THREADS) lamb_apply_kernel(const float* a, const float* update, const float* rate_trust, float* b, const size_t n)
-{
-	const float rt = *rate_trust;
-	const size_t stride = (size_t)gridDim.x * blockDim.x;
-	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) b[i] = a[i] - rt * update[i];
-}
+// ---- LAMB: update = mom^ / (sqrt(vel^) + eps) + decay w; b = a - rate (|w| / |update|) update.  Three launches (optim.h lamb_run): the element pass writes n, u
+// and the update (workspace, fp32) and one (sum w^2, sum update^2) pair per workgroup in double; one thread folds the pairs in order into the trust
+// ratio; the last pass applies it.  Deterministic. -------------------------------------------------------------------------------------
 static int _lamb_forw(EXEC_ARGS)
 {
 	if (input_size < 4 || output_size < 3) return CCV_NNC_EXEC_INVALID;
-	for (int i = 0; i < 4; i++) if (!dense_f32(inputs[i])) return CCV_NNC_EXEC_INVALID;
-	for (int i = 0; i < 3; i++) if (!dense_f32(outputs[i])) return CCV_NNC_EXEC_INVALID;
-	const size_t n = tensor_count(inputs[1]->info);
-	for (int i = 0; i < 4; i++) if (tensor_count(inputs[i]->info) != n) return CCV_NNC_EXEC_INVALID;
-	for (int i = 0; i < 3; i++) if (tensor_count(outputs[i]->info) != n) return CCV_NNC_EXEC_INVALID;
+	int tg, tp;
+	size_t n;
+	const int bad = opt_tensors(inputs, 4, outputs, 3, &tg, &tp, &n);
+	if (bad) return bad;
 	if (n == 0) return CCV_NNC_EXEC_SUCCESS;
-	int blocks = grid_for(n, EW_THREADS); // one partial norm pair per workgroup, folded by one thread: keep them few
-	if (blocks > device_cu_count() * 8) blocks = device_cu_count() * 8;
-	const size_t head = (sizeof(double) * 2 * (size_t)blocks + sizeof(float) + 255) & ~(size_t)255;
-	char* ws = (char*)workspace_of(stream_context, head + sizeof(float) * n);
-	if (!ws) return CCV_NNC_EXEC_OOM;
-	double* const partial = (double*)ws;
-	float* const rate_trust = (float*)(ws + sizeof(double) * 2 * (size_t)blocks);
-	float* const update = (float*)(ws + head);
-	LambP p;
+	optim::LambUpdateOp p;
 	p.scale = cmd.info.lamb.scale; p.beta1 = cmd.info.lamb.beta1; p.beta2 = cmd.info.lamb.beta2; p.decay = cmd.info.lamb.decay; p.epsilon = cmd.info.lamb.epsilon;
 	p.inv_corr1 = 1.f / (1 - powf(p.beta1, (float)cmd.info.lamb.step));
 	p.inv_corr2 = 1.f / (1 - powf(p.beta2, (float)cmd.info.lamb.step));
-	hipStream_t stream = stream_of(stream_context);
-	hipLaunchKernelGGL(lamb_update_kernel, dim3(blocks), dim3(EW_THREADS), 0, stream, p, (const float*)inputs[0]->data.f32, (const float*)inputs[1]->data.f32, (const float*)inputs[2]->data.f32, (const float*)inputs[3]->data.f32,
-		outputs[1]->data.f32, outputs[2]->data.f32, update, partial, n);
-	hipLaunchKernelGGL(lamb_trust_kernel, dim3(1), dim3(1), 0, stream, (const double*)partial, blocks, cmd.info.lamb.rate, rate_trust);
-	hipLaunchKernelGGL(lamb_apply_kernel, dim3(blocks), dim3(EW_THREADS), 0, stream, (const float*)inputs[1]->data.f32, (const float*)update, (const float*)rate_trust, outputs[0]->data.f32, n);
-	HIP_ENFORCE(hipGetLastError());
-	return CCV_NNC_EXEC_SUCCESS;
+#define LAMB_CALL(TG, TP) optim::lamb_run<TG, TP>(p, cmd.info.lamb.rate, (const TG*)inputs[0]->data.u8, (const TP*)inputs[1]->data.u8, (const TP*)inputs[2]->data.u8, (const TP*)inputs[3]->data.u8, (TP*)outputs[0]->data.u8, (TP*)outputs[1]->data.u8, (TP*)outputs[2]->data.u8, n, stream_context)
+	return OPT_DISPATCH(tg, tp, LAMB_CALL);
+#undef LAMB_CALL
 }
 
 } // namespace

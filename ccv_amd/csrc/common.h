@@ -274,6 +274,7 @@ enum {
 	TUNE_CONV_DEPTHWISE,    // depthwise convolutions (groups == channels == filters, dense tensors of one type and one format) on the direct stencil kernels of conv_depthwise.h (1), or as `groups` one-column implicit GEMMs (0)
 	TUNE_ACT_HALF_NATIVE,   // the activations (sigmoid, tanh, GELU, swish, leaky ReLU; forward and backward) and dropout read and write CCV_16F tensors as halves themselves (1), or run on fp32 images of them (0)
 	TUNE_MUL_PLANES,        // MUL of a dense 4-d activation tensor by a per-(image, channel) vector (squeeze-excite), forward and backward, fp32 and half, on the plane-scale kernels of mul_planes.h (1), or the generic broadcast map / reduce kernels (0)
+	TUNE_OPT_HALF_NATIVE,   // RMSPROP, ADAM, ADAMW and LAMB read and write CCV_16F tensors as halves themselves -- all tensors half, only g half, or only the parameter and state tensors half (optim.h) -- (1), or run on fp32 images of them (0)
 	TUNE_COUNT
 };
 static_assert(TUNE_GRID_WG_PER_CU == 3, "grid_for() above names this key by value");

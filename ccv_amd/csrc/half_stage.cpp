@@ -171,6 +171,14 @@ struct native_half_t { uint32_t cmd; unsigned in, out; native_when_f when; };
 static bool act_native(const ccv_nnc_cmd_t, int, ccv_nnc_tensor_t* const*, int, ccv_nnc_tensor_t* const*, int) { return tune(TUNE_ACT_HALF_NATIVE) != 0; }
 // the backward commands without g (ones) keep their fp32 kernels (cmd_act_opt.cpp)
 static bool act_back_native(const ccv_nnc_cmd_t, int, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const*, int) { return tune(TUNE_ACT_HALF_NATIVE) != 0 && input_size > 0 && inputs[0]; }
+// the optimizers (cmd_act_opt.cpp, optim.h): the amsgrad tensors (input 4, output 3) belong to the state tensors when present
+constexpr unsigned OPT_G = 1u << 0, OPT_STATE_IN = (1u << 1) | (1u << 2) | (1u << 3) | (1u << 4), OPT_STATE_OUT = (1u << 0) | (1u << 1) | (1u << 2) | (1u << 3);
+static bool opt_native(const ccv_nnc_cmd_t, int, ccv_nnc_tensor_t* const*, int, ccv_nnc_tensor_t* const*, int) { return tune(TUNE_OPT_HALF_NATIVE) != 0; }
+static bool none_half(ccv_nnc_tensor_t* const* ts, const int from, const int size) { for (int i = from; i < size; i++) if (ts[i] && CCV_GET_DATA_TYPE(ts[i]->info.datatype) == CCV_16F) return false; return true; }
+// g alone: no other tensor is a half one (state tensors of two types keep their fp32 images)
+static bool opt_g_native(const ccv_nnc_cmd_t, int, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size) { return tune(TUNE_OPT_HALF_NATIVE) != 0 && none_half(inputs, 1, input_size) && none_half(outputs, 0, output_size); }
+// the state tensors alone: g is not a half tensor
+static bool opt_state_native(const ccv_nnc_cmd_t, int, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const*, int) { return tune(TUNE_OPT_HALF_NATIVE) != 0 && none_half(inputs, 0, input_size < 1 ? input_size : 1); }
 static const native_half_t g_native_half[] = {
 	{ CCV_NNC_RELU_FORWARD, 1u << 0, 1u << 0 },
 	{ CCV_NNC_RELU_BACKWARD, (1u << 0) | (1u << 2), 1u << 0 },            // g, (a unused), b -> h
@@ -201,6 +209,14 @@ static const native_half_t g_native_half[] = {
 	// cmd_bcast.cpp: only the squeeze-excite pattern of mul_planes.h; every other MUL runs on fp32 images
 	{ CCV_NNC_MUL_FORWARD, (1u << 0) | (1u << 1), 1u << 0, mul_planes_applies },            // a, b -> c
 	{ CCV_NNC_MUL_BACKWARD, (1u << 0) | (1u << 1) | (1u << 2), (1u << 0) | (1u << 1), mul_planes_applies }, // g, a, b -> da, db
+	// optim.h: g, a, m, v[, vm] -> b, n, u[, um].  Three rows per command, tried in order: every tensor half; g alone (half gradients into fp32 master
+	// parameters); the parameter and state tensors alone (fp32 gradients)
+#define OPT_ROWS(CMD) { CMD, OPT_G | OPT_STATE_IN, OPT_STATE_OUT, opt_native }, { CMD, OPT_G, 0, opt_g_native }, { CMD, OPT_STATE_IN, OPT_STATE_OUT, opt_state_native }
+	OPT_ROWS(CCV_NNC_RMSPROP_FORWARD),
+	OPT_ROWS(CCV_NNC_ADAM_FORWARD),
+	OPT_ROWS(CCV_NNC_ADAMW_FORWARD),
+	OPT_ROWS(CCV_NNC_LAMB_FORWARD),
+#undef OPT_ROWS
 };
 static const native_half_t* native_half_row(const ccv_nnc_cmd_t command, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
 {
@@ -209,11 +225,13 @@ static const native_half_t* native_half_row(const ccv_nnc_cmd_t command, const i
 	for (const native_half_t& r : g_native_half) {
 		if (r.cmd != cmd) continue;
 		int seen = 0;
-		for (int i = 0; i < input_size && i < 32; i++)
-			if (((r.in >> i) & 1) && inputs[i]) { if (CCV_GET_DATA_TYPE(inputs[i]->info.datatype) != CCV_16F || CCV_IS_TENSOR_VIEW(inputs[i])) return 0; seen++; }
-		for (int i = 0; i < output_size && i < 32; i++)
-			if (((r.out >> i) & 1) && outputs[i]) { if (CCV_GET_DATA_TYPE(outputs[i]->info.datatype) != CCV_16F || CCV_IS_TENSOR_VIEW(outputs[i])) return 0; seen++; }
-		return seen && (!r.when || r.when(command, flags, inputs, input_size, outputs, output_size)) ? &r : 0;
+		bool fits = true;
+		for (int i = 0; fits && i < input_size && i < 32; i++)
+			if (((r.in >> i) & 1) && inputs[i]) { fits = CCV_GET_DATA_TYPE(inputs[i]->info.datatype) == CCV_16F && !CCV_IS_TENSOR_VIEW(inputs[i]); seen++; }
+		for (int i = 0; fits && i < output_size && i < 32; i++)
+			if (((r.out >> i) & 1) && outputs[i]) { fits = CCV_GET_DATA_TYPE(outputs[i]->info.datatype) == CCV_16F && !CCV_IS_TENSOR_VIEW(outputs[i]); seen++; }
+		if (fits && seen && (!r.when || r.when(command, flags, inputs, input_size, outputs, output_size))) return &r;
+		// (a command may have several rows -- the optimizers' type combinations: the next one of the same command is tried)
 	}
 	return 0;
 }
