@@ -14,6 +14,7 @@
 //   lamb        lib/nnc/cmd/lamb/ccv_nnc_lamb_cpu_ref.c:16-140             Adam-style update scaled per TENSOR by |w| / |update| (norms in double)
 #include "common.h"
 #include "optim.h"
+#include "row_ops.h"
 
 using namespace nnc;
 
@@ -194,8 +195,27 @@ __global__ void __launch_bounds__(256) softmax_back_kernel(const float* g, const
 	s = block_reduce(s, red, false);
 	for (int j = threadIdx.x; j < count; j += 256) h[o + j] = (g[o + j] - s) * b[o + j];
 }
+// rows = dim[0] (1-d: one row)
+static int softmax_batch(const ccv_nnc_tensor_t* a) { return tensor_nd(a->info.dim) < 2 ? 1 : a->info.dim[0]; }
+static bool is_half(const ccv_nnc_tensor_t* t) { return t && CCV_GET_DATA_TYPE(t->info.datatype) == CCV_16F; }
+// CCV_16F tensors (half_stage.cpp g_native_half, tunable ROW_HALF_NATIVE): the row kernels of row_ops.h -- the row in registers, b written once
+static int softmax_half(const ccv_nnc_tensor_t* g, const ccv_nnc_tensor_t* ab, ccv_nnc_tensor_t* out, ccv_nnc_stream_context_t* const ctx)
+{ // forward: (0, a, b); backward: (g, b, h)
+	if (!dense_of(ab, CCV_16F) || !dense_of(out, CCV_16F) || !same_count(ab, out) || (g && (!dense_of(g, CCV_16F) || !same_count(g, ab)))) return CCV_NNC_EXEC_INVALID;
+	const ccv_nnc_tensor_t* const first = g ? g : ab;
+	const int batch = softmax_batch(first);
+	const size_t n = tensor_count(first->info);
+	if (n == 0) return CCV_NNC_EXEC_SUCCESS;
+	if (batch < 1 || n / batch > (size_t)rows::ROW_REG_MAX) return CCV_NNC_EXEC_INVALID;
+	rows::softmax_args_t p = {};
+	p.rows = batch; p.n = (int)(n / batch);
+	if (g) { p.g = g->data.u8; p.b_in = ab->data.u8; p.h = out->data.u8; return rows::softmax_bwd<rows::half_t>(p, ctx); }
+	p.a = ab->data.u8; p.b = out->data.u8;
+	return rows::softmax_fwd<rows::half_t>(p, ctx);
+}
 static int _softmax_forw(EXEC_ARGS)
 {
+	if (input_size >= 1 && output_size >= 1 && is_half(inputs[0])) return softmax_half(0, inputs[0], outputs[0], stream_context);
 	if (input_size < 1 || output_size < 1 || !dense_f32(inputs[0]) || !dense_f32(outputs[0]) || !same_count(inputs[0], outputs[0])) return CCV_NNC_EXEC_INVALID;
 	const ccv_nnc_tensor_t* a = inputs[0];
 	const int batch = tensor_nd(a->info.dim) < 2 ? 1 : a->info.dim[0];
@@ -207,6 +227,7 @@ static int _softmax_forw(EXEC_ARGS)
 }
 static int _softmax_back(EXEC_ARGS)
 {
+	if (input_size >= 3 && output_size >= 1 && is_half(inputs[0])) return softmax_half(inputs[0], inputs[2], outputs[0], stream_context);
 	if (input_size < 3 || output_size < 1 || !dense_f32(inputs[0]) || !dense_f32(inputs[2]) || !dense_f32(outputs[0]) || !same_count(inputs[0], inputs[2]) || !same_count(inputs[0], outputs[0])) return CCV_NNC_EXEC_INVALID;
 	const ccv_nnc_tensor_t* g = inputs[0];
 	const int batch = tensor_nd(g->info.dim) < 2 ? 1 : g->info.dim[0];
@@ -310,6 +331,14 @@ static int _lamb_forw(EXEC_ARGS)
 }
 
 } // namespace
+
+bool nnc::softmax_half_applies(const ccv_nnc_cmd_t cmd, int, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
+{
+	if (!tune(TUNE_ROW_HALF_NATIVE) || input_size < 1 || !inputs[0]) return false;
+	const size_t n = tensor_count(inputs[0]->info);
+	const int batch = softmax_batch(inputs[0]);
+	return batch >= 1 && n / batch <= (size_t)rows::ROW_REG_MAX;
+}
 
 #define NNC_REG(CMD, BACKEND, FORMATS, EXEC) \
 	extern "C" void _register_command_##CMD##_backend_##BACKEND(ccv_nnc_cmd_backend_registry_t* const registry) \

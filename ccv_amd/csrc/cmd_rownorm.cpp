@@ -10,7 +10,10 @@
 // n elements (or a single one); other reduce-axis patterns return CCV_NNC_EXEC_INVALID.  One 256-thread block per row; a row is read from
 // HBM once and re-read from L1/L2 for the later passes; parameter gradients are row-chunk partial sums folded by colsum_f32 (fixed order).
 // HBM-bound: forward 2 |a|, backward 3 |a| bytes.
+// CCV_16F maps (half_stage.cpp g_native_half, tunable ROW_HALF_NATIVE) take the row kernels of row_ops.h instead: the row in registers, read once, at most two
+// launches; the parameters and statistics are halves too ("hh") or fp32 tensors / images ("hf").  The fp32 commands keep the kernels below and their bits.
 #include "chan_sums.h"
+#include "row_ops.h"
 
 using namespace nnc;
 
@@ -105,10 +108,11 @@ static bool row_geometry(const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* stat
 	*rows = (int)r; *n = (int)m;
 	return true;
 }
-static bool param_inc(const ccv_nnc_tensor_t* p, const int n, int* inc)
+static bool dense_of(const ccv_nnc_tensor_t* t, const int dt) { return t && tensor_contiguous(t) && CCV_GET_DATA_TYPE(t->info.datatype) == dt; }
+static bool param_inc(const ccv_nnc_tensor_t* p, const int n, int* inc, const int dt = CCV_32F)
 {
 	if (!p) { *inc = 0; return true; }
-	if (!dense_f32(p)) return false;
+	if (!dense_of(p, dt)) return false;
 	const size_t c = tensor_count(p->info);
 	if (c == (size_t)n) { *inc = 1; return true; }
 	if (c == 1) { *inc = 0; return true; }
@@ -117,9 +121,45 @@ static bool param_inc(const ccv_nnc_tensor_t* p, const int n, int* inc)
 
 #define EXEC_ARGS const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context
 
+// ---- CCV_16F maps: row_ops.h.  The parameters and statistics share ONE type, half or fp32 (half_stage.cpp hands over either every used tensor as it is, or
+// the maps alone and fp32 images of the rest) ----
+static int stat_type(const ccv_nnc_tensor_t* t) { const int dt = t ? CCV_GET_DATA_TYPE(t->info.datatype) : 0; return dt == CCV_16F || dt == CCV_32F ? dt : 0; }
+template <bool CENTER>
+static int rownorm_forw_half(const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* scale, const ccv_nnc_tensor_t* bias, ccv_nnc_tensor_t* b, ccv_nnc_tensor_t* saved_mean, ccv_nnc_tensor_t* saved_inv_std, const float epsilon, ccv_nnc_stream_context_t* const ctx)
+{
+	const int pt = stat_type(saved_inv_std);
+	if (!pt || !dense_of(a, CCV_16F) || !dense_of(b, CCV_16F) || !dense_of(saved_inv_std, pt) || (CENTER && !dense_of(saved_mean, pt)) || tensor_count(a->info) != tensor_count(b->info)) return CCV_NNC_EXEC_INVALID;
+	rows::norm_args_t p = {};
+	if (!row_geometry(a, saved_inv_std, &p.rows, &p.n) || p.n > rows::ROW_REG_MAX || !param_inc(scale, p.n, &p.scale_inc, pt) || !param_inc(bias, p.n, &p.bias_inc, pt)) return CCV_NNC_EXEC_INVALID;
+	if (CENTER && tensor_count(saved_mean->info) != (size_t)p.rows) return CCV_NNC_EXEC_INVALID;
+	p.a = a->data.u8; p.b = b->data.u8;
+	p.scale = scale ? scale->data.u8 : 0; p.bias = bias ? bias->data.u8 : 0;
+	p.mean = CENTER ? saved_mean->data.u8 : 0; p.inv_std = saved_inv_std->data.u8;
+	p.epsilon = epsilon;
+	return pt == CCV_16F ? rows::norm_fwd<rows::half_t, rows::half_t, CENTER>(p, ctx) : rows::norm_fwd<rows::half_t, float, CENTER>(p, ctx);
+}
+template <bool CENTER>
+static int rownorm_back_half(const ccv_nnc_tensor_t* g, const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* scale, const ccv_nnc_tensor_t* saved_mean, const ccv_nnc_tensor_t* saved_inv_std, ccv_nnc_tensor_t* h, ccv_nnc_tensor_t* dscale, ccv_nnc_tensor_t* dbias, ccv_nnc_stream_context_t* const ctx)
+{
+	const int pt = stat_type(saved_inv_std);
+	if (!pt || !dense_of(g, CCV_16F) || !dense_of(a, CCV_16F) || !dense_of(saved_inv_std, pt) || (CENTER && !dense_of(saved_mean, pt)) || tensor_count(g->info) != tensor_count(a->info)) return CCV_NNC_EXEC_INVALID;
+	rows::norm_args_t p = {};
+	if (!row_geometry(a, saved_inv_std, &p.rows, &p.n) || p.n > rows::ROW_REG_MAX || !param_inc(scale, p.n, &p.scale_inc, pt)) return CCV_NNC_EXEC_INVALID;
+	if (h && (!dense_of(h, CCV_16F) || tensor_count(h->info) != tensor_count(a->info))) return CCV_NNC_EXEC_INVALID;
+	if (dbias && (!dense_of(dbias, pt) || tensor_count(dbias->info) != (size_t)p.n)) return CCV_NNC_EXEC_INVALID;
+	if (dscale && (!dense_of(dscale, pt) || tensor_count(dscale->info) != (size_t)p.n)) return CCV_NNC_EXEC_INVALID;
+	p.g = g->data.u8; p.a = a->data.u8; p.h = h ? h->data.u8 : 0;
+	p.scale = scale ? scale->data.u8 : 0;
+	p.mean_in = CENTER ? saved_mean->data.u8 : 0; p.inv_std_in = saved_inv_std->data.u8;
+	if (pt == CCV_16F) return rows::norm_bwd<rows::half_t, rows::half_t, CENTER>(p, dscale ? (rows::half_t*)dscale->data.u8 : 0, dbias ? (rows::half_t*)dbias->data.u8 : 0, ctx);
+	return rows::norm_bwd<rows::half_t, float, CENTER>(p, dscale ? dscale->data.f32 : 0, dbias ? dbias->data.f32 : 0, ctx);
+}
+static bool is_half(const ccv_nnc_tensor_t* t) { return t && CCV_GET_DATA_TYPE(t->info.datatype) == CCV_16F; }
+
 template <bool CENTER>
 static int rownorm_forw(const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* scale, const ccv_nnc_tensor_t* bias, ccv_nnc_tensor_t* b, ccv_nnc_tensor_t* saved_mean, ccv_nnc_tensor_t* saved_inv_std, const float epsilon, ccv_nnc_stream_context_t* const ctx)
 {
+	if (is_half(a)) return rownorm_forw_half<CENTER>(a, scale, bias, b, saved_mean, saved_inv_std, epsilon, ctx);
 	if (!dense_f32(a) || !dense_f32(b) || !dense_f32(saved_inv_std) || (CENTER && !dense_f32(saved_mean)) || tensor_count(a->info) != tensor_count(b->info)) return CCV_NNC_EXEC_INVALID;
 	int rows, n, sinc, binc;
 	if (!row_geometry(a, saved_inv_std, &rows, &n) || !param_inc(scale, n, &sinc) || !param_inc(bias, n, &binc)) return CCV_NNC_EXEC_INVALID;
@@ -133,6 +173,7 @@ static int rownorm_forw(const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* scale
 template <bool CENTER>
 static int rownorm_back(const ccv_nnc_tensor_t* g, const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* scale, const ccv_nnc_tensor_t* saved_mean, const ccv_nnc_tensor_t* saved_inv_std, ccv_nnc_tensor_t* h, ccv_nnc_tensor_t* dscale, ccv_nnc_tensor_t* dbias, ccv_nnc_stream_context_t* const ctx)
 {
+	if (is_half(a)) return rownorm_back_half<CENTER>(g, a, scale, saved_mean, saved_inv_std, h, dscale, dbias, ctx);
 	if (!dense_f32(g) || !dense_f32(a) || !dense_f32(saved_inv_std) || (CENTER && !dense_f32(saved_mean)) || tensor_count(g->info) != tensor_count(a->info)) return CCV_NNC_EXEC_INVALID;
 	int rows, n, sinc;
 	if (!row_geometry(a, saved_inv_std, &rows, &n) || !param_inc(scale, n, &sinc)) return CCV_NNC_EXEC_INVALID;
@@ -199,6 +240,28 @@ static int _rmsnorm_back(EXEC_ARGS)
 }
 
 } // namespace
+
+// half_stage.cpp asks before it leaves the command's half tensors in their own memory (the masks have matched: the tensors they name are dense halves)
+bool nnc::rownorm_half_applies(const ccv_nnc_cmd_t cmd, int, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
+{
+	if (!tune(TUNE_ROW_HALF_NATIVE)) return false;
+	const ccv_nnc_tensor_t *a = 0, *stat = 0, *scale = 0, *bias = 0;
+	auto in = [&](const int i) { return i < input_size ? inputs[i] : 0; };
+	auto out = [&](const int i) { return i < output_size ? outputs[i] : 0; };
+	const int affine = cmd.info.lnorm.elementwise_affine;
+	switch (cmd.cmd) {
+		case CCV_NNC_LAYER_NORM_FORWARD: a = in(0); stat = out(2); if (affine) { scale = in(1); bias = in(2); if (!scale || !bias) return false; } break;
+		case CCV_NNC_LAYER_NORM_BACKWARD: a = in(3); stat = in(affine ? 8 : 6); if (affine) { scale = in(4); if (!scale) return false; } break;
+		case CCV_NNC_RMSNORM_FORWARD: a = in(0); scale = in(1); stat = out(1); if (!scale) return false; break;
+		case CCV_NNC_RMSNORM_BACKWARD: a = in(2); scale = in(3); stat = in(5); if (!scale) return false; break;
+		default: return false;
+	}
+	int rows, n;
+	if (!a || !stat || !row_geometry(a, stat, &rows, &n) || n > rows::ROW_REG_MAX) return false;
+	for (const ccv_nnc_tensor_t* const p : { scale, bias })
+		if (p) { const size_t c = tensor_count(p->info); if (c != (size_t)n && c != 1) return false; }
+	return true;
+}
 
 #define NNC_REG(CMD, BACKEND, EXEC) \
 	extern "C" void _register_command_##CMD##_backend_##BACKEND(ccv_nnc_cmd_backend_registry_t* const registry) \

@@ -275,6 +275,7 @@ enum {
 	TUNE_ACT_HALF_NATIVE,   // the activations (sigmoid, tanh, GELU, swish, leaky ReLU; forward and backward) and dropout read and write CCV_16F tensors as halves themselves (1), or run on fp32 images of them (0)
 	TUNE_MUL_PLANES,        // MUL of a dense 4-d activation tensor by a per-(image, channel) vector (squeeze-excite), forward and backward, fp32 and half, on the plane-scale kernels of mul_planes.h (1), or the generic broadcast map / reduce kernels (0)
 	TUNE_OPT_HALF_NATIVE,   // RMSPROP, ADAM, ADAMW and LAMB read and write CCV_16F tensors as halves themselves -- all tensors half, only g half, or only the parameter and state tensors half (optim.h) -- (1), or run on fp32 images of them (0)
+	TUNE_ROW_HALF_NATIVE,   // LAYER_NORM, RMSNORM and plain SOFTMAX, forward and backward, read and write CCV_16F maps as halves themselves on the row kernels of row_ops.h -- every used tensor half, or only the maps -- (1), or run on fp32 images of them (0)
 	TUNE_COUNT
 };
 static_assert(TUNE_GRID_WG_PER_CU == 3, "grid_for() above names this key by value");
@@ -324,6 +325,10 @@ static int half_staged(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const
 // cmd_bcast.cpp: is this MUL_FORWARD / MUL_BACKWARD command one the plane-scale kernels (mul_planes.h) take?  The row asks before it routes; half_stage.cpp asks
 // before it leaves the command's half tensors in their own memory -- one answer for both.
 bool mul_planes_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size);
+// cmd_rownorm.cpp / cmd_act_opt.cpp: is this LAYER_NORM / RMSNORM / SOFTMAX command (forward or backward) one the half row kernels (row_ops.h) take -- tuning key,
+// rows x n geometry, n <= ROW_REG_MAX, parameters of n elements or one?  (Types and views are the masks' business in half_stage.cpp.)
+bool rownorm_half_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size);
+bool softmax_half_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size);
 bool any_half_tensor(ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size);
 int half_to_float(const void* in, float* out, size_t n, ccv_nnc_stream_context_t* ctx);
 int float_to_half(const float* in, void* out, size_t n, ccv_nnc_stream_context_t* ctx);

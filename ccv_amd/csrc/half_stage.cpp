@@ -145,7 +145,7 @@ void warn_refused(const uint32_t cmd, const int ret)
 }
 
 // Rows whose kernels read and write their LARGE tensors in half precision themselves (loads / stores of halves, fp32 arithmetic:
-// cmd_ew.cpp, cmd_norm.cpp, cmd_pool.cpp, cmd_act_opt.cpp, cmd_bcast.cpp's plane-scale MUL).  Bit i of `in` / `out` = that input / output stays in its own memory when every tensor
+// cmd_ew.cpp, cmd_norm.cpp, cmd_pool.cpp, cmd_act_opt.cpp, cmd_bcast.cpp's plane-scale MUL, row_ops.h).  Bit i of `in` / `out` = that input / output stays in its own memory when every tensor
 // named by the masks is a dense CCV_16F tensor; the row's small tensors (batch-norm statistics, ...) still get fp32 images.
 static long g_half_staged = 0, g_half_native = 0; // nnc_mi355x_debug_half_counts (test hook; not synchronised: counts, not control)
 // NNC_MI355X_HALF_STATS=1: one line per command at unload -- which rows of a run went through fp32 images of their half tensors (and how many tensors)
@@ -179,6 +179,9 @@ static bool none_half(ccv_nnc_tensor_t* const* ts, const int from, const int siz
 static bool opt_g_native(const ccv_nnc_cmd_t, int, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size) { return tune(TUNE_OPT_HALF_NATIVE) != 0 && none_half(inputs, 1, input_size) && none_half(outputs, 0, output_size); }
 // the state tensors alone: g is not a half tensor
 static bool opt_state_native(const ccv_nnc_cmd_t, int, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const*, int) { return tune(TUNE_OPT_HALF_NATIVE) != 0 && none_half(inputs, 0, input_size < 1 ? input_size : 1); }
+// row_ops.h: LAYER_NORM (affine and not: the statistics sit in other slots), RMSNORM, SOFTMAX.  The predicates are cmd_rownorm.cpp's / cmd_act_opt.cpp's
+static bool lnorm_affine_native(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size) { return cmd.info.lnorm.elementwise_affine && rownorm_half_applies(cmd, flags, inputs, input_size, outputs, output_size); }
+static bool lnorm_plain_native(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size) { return !cmd.info.lnorm.elementwise_affine && rownorm_half_applies(cmd, flags, inputs, input_size, outputs, output_size); }
 static const native_half_t g_native_half[] = {
 	{ CCV_NNC_RELU_FORWARD, 1u << 0, 1u << 0 },
 	{ CCV_NNC_RELU_BACKWARD, (1u << 0) | (1u << 2), 1u << 0 },            // g, (a unused), b -> h
@@ -217,6 +220,20 @@ static const native_half_t g_native_half[] = {
 	OPT_ROWS(CCV_NNC_ADAMW_FORWARD),
 	OPT_ROWS(CCV_NNC_LAMB_FORWARD),
 #undef OPT_ROWS
+	// row_ops.h.  Two rows per command (and per layer-norm variant), tried in order: every USED tensor half ("hh": what an all-half graph issues -- the parameters
+	// and statistics take the input's type); the maps alone ("hf": a half parameter or statistic gets its small fp32 image).  Unused slots are not named.
+	{ CCV_NNC_LAYER_NORM_FORWARD, (1u << 0) | (1u << 1) | (1u << 2), (1u << 0) | (1u << 1) | (1u << 2), lnorm_affine_native }, // a, scale, bias -> b, saved_mean, saved_inv_std
+	{ CCV_NNC_LAYER_NORM_FORWARD, 1u << 0, (1u << 0) | (1u << 1) | (1u << 2), lnorm_plain_native },                            // a -> b, saved_mean, saved_inv_std
+	{ CCV_NNC_LAYER_NORM_FORWARD, 1u << 0, 1u << 0, rownorm_half_applies },
+	{ CCV_NNC_LAYER_NORM_BACKWARD, (1u << 0) | (1u << 3) | (1u << 4) | (1u << 7) | (1u << 8), (1u << 0) | (1u << 1) | (1u << 2), lnorm_affine_native }, // g, a, scale, saved_mean, saved_inv_std -> h, dscale, dbias
+	{ CCV_NNC_LAYER_NORM_BACKWARD, (1u << 0) | (1u << 3) | (1u << 5) | (1u << 6), (1u << 0) | (1u << 1) | (1u << 2), lnorm_plain_native },             // g, a, saved_mean, saved_inv_std -> h
+	{ CCV_NNC_LAYER_NORM_BACKWARD, (1u << 0) | (1u << 3), 1u << 0, rownorm_half_applies },
+	{ CCV_NNC_RMSNORM_FORWARD, (1u << 0) | (1u << 1), (1u << 0) | (1u << 1), rownorm_half_applies },                           // a, scale -> b, saved_inv_std
+	{ CCV_NNC_RMSNORM_FORWARD, 1u << 0, 1u << 0, rownorm_half_applies },
+	{ CCV_NNC_RMSNORM_BACKWARD, (1u << 0) | (1u << 2) | (1u << 3) | (1u << 5), (1u << 0) | (1u << 1), rownorm_half_applies },  // g, a, scale, saved_inv_std -> h, dscale
+	{ CCV_NNC_RMSNORM_BACKWARD, (1u << 0) | (1u << 2), 1u << 0, rownorm_half_applies },
+	{ CCV_NNC_SOFTMAX_FORWARD, 1u << 0, 1u << 0, softmax_half_applies },                                                       // a -> b
+	{ CCV_NNC_SOFTMAX_BACKWARD, (1u << 0) | (1u << 2), 1u << 0, softmax_half_applies },                                        // g, (a unused), b -> h
 };
 static const native_half_t* native_half_row(const ccv_nnc_cmd_t command, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
 {
