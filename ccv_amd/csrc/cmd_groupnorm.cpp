@@ -9,7 +9,9 @@
 // which in the parameter union overlays gnorm.reduce_count -- an int of 1..3 seen as a float, i.e. ~1e-45, not the 1e-5 the caller passed.
 // Results must match the reference's, so the same field is read (with small groups the difference, eps / (2 var), reaches 5e-5).
 // One 256-thread block per statistic (forward, h) or per scale element (parameter gradients); dense tensors only.  HBM-bound.
-#include "common.h"
+// CCV_16F maps (half_stage.cpp g_native_half, tunable GNORM_HALF_NATIVE) take the kernels of group_ops.h instead where half_operands() below finds one of
+// its two layouts; the fp32 commands, and every other half command on its fp32 images, keep the kernels below and their bits.
+#include "group_ops.h"
 
 using namespace nnc;
 
@@ -167,8 +169,105 @@ static bool geometry(const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* stat, co
 
 #define EXEC_ARGS const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context
 
+// ---- CCV_16F maps: group_ops.h.  The parameters and statistics share ONE type, half or fp32 (half_stage.cpp hands over either every used tensor as it is, or
+// the maps alone and fp32 images of the rest).  The predicate and the two launchers pick the command's tensors and its shape with the same function. ----
+static bool is_half(const ccv_nnc_tensor_t* t) { return t && CCV_GET_DATA_TYPE(t->info.datatype) == CCV_16F; }
+static bool dense_of(const ccv_nnc_tensor_t* t, const int dt) { return t && tensor_contiguous(t) && CCV_GET_DATA_TYPE(t->info.datatype) == dt; }
+static int stat_type(const ccv_nnc_tensor_t* t) { const int dt = t ? CCV_GET_DATA_TYPE(t->info.datatype) : 0; return dt == CCV_16F || dt == CCV_32F ? dt : 0; }
+struct half_ops_t {
+	const ccv_nnc_tensor_t *a, *g, *scale, *bias, *mean, *inv_std; // (backward: the stored statistics)
+	ccv_nnc_tensor_t *out, *dscale, *dbias; // out: b or h
+	gnorm::shape_t shape;
+};
+// the axis on which a parameter tensor has all of its elements, exactly as many as the map has there; -1: another extent pattern
+static int param_axis(const int (&ad)[4], const int (&pd)[4])
+{
+	int j = -1;
+	for (int k = 0; k < 4; k++)
+		if (pd[k] != 1) { if (j >= 0 || pd[k] != ad[k]) return -1; j = k; }
+	return j;
+}
+// planar: block extents 1 before some axis j, anything on it, the map's behind it (parameters on j).  inter: NHWC, groups on axis 3, reduced over (1, 2).
+static bool half_shape(const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* stat, const ccv_nnc_tensor_t* const (&params)[3], gnorm::shape_t* s)
+{
+	GnGeom g;
+	if (!a || !stat || !geometry(a, stat, 0, 0, &g) || prod(g.ad) == 0) return false;
+	int jp = -1, e[4];
+	for (const ccv_nnc_tensor_t* const p : params)
+		if (p) {
+			int pd[4];
+			if (!dims4(p, pd)) return false;
+			const int j = param_axis(g.ad, pd);
+			if (j < 0 || (jp >= 0 && j != jp)) return false;
+			jp = j;
+		}
+	for (int k = 0; k < 4; k++) e[k] = g.ad[k] / g.rd[k];
+	int j = jp;
+	if (j < 0) { j = 3; for (int k = 0; k < 4; k++) if (e[k] != 1) { j = k; break; } }
+	bool planar = true;
+	for (int k = 0; k < 4; k++) if (k != j && e[k] != (k < j ? 1 : g.ad[k])) planar = false;
+	long outer = 1, inner = 1;
+	if (planar) {
+		for (int k = 0; k < j; k++) outer *= g.ad[k];
+		for (int k = j + 1; k < 4; k++) inner *= g.ad[k];
+		s->inter = 0; s->C = g.ad[j]; s->G = g.rd[j];
+	} else if ((jp < 0 || jp == 3) && e[0] == 1 && e[1] == g.ad[1] && e[2] == g.ad[2]) {
+		outer = g.ad[0]; inner = (long)g.ad[1] * g.ad[2];
+		s->inter = 1; s->C = g.ad[3]; s->G = g.rd[3];
+	} else return false;
+	s->outer = (int)outer; s->inner = (int)inner; s->cg = s->C / s->G;
+	s->n = (int)(s->cg * inner); s->R = (int)(outer * s->G);
+	return gnorm::shape_served(*s);
+}
+static bool half_operands(const ccv_nnc_cmd_t cmd, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, half_ops_t* const o)
+{
+	auto in = [&](const int i) { return i < input_size ? inputs[i] : 0; };
+	auto out = [&](const int i) { return i < output_size ? outputs[i] : 0; };
+	const int affine = cmd.info.gnorm.elementwise_affine;
+	*o = half_ops_t();
+	if (cmd.cmd == CCV_NNC_GROUP_NORM_FORWARD) {
+		o->a = in(0); o->out = out(0); o->mean = out(1); o->inv_std = out(2);
+		if (affine) { o->scale = in(1); o->bias = in(2); if (!o->scale || !o->bias) return false; }
+		if (!o->out) return false;
+	} else if (cmd.cmd == CCV_NNC_GROUP_NORM_BACKWARD) {
+		o->g = in(0); o->a = in(3); o->mean = in(affine ? 7 : 5); o->inv_std = in(affine ? 8 : 6);
+		if (affine) { o->scale = in(4); if (!o->scale) return false; }
+		o->out = out(0); o->dscale = out(1); o->dbias = out(2);
+		if (!o->g) return false;
+	} else return false;
+	if (!o->mean || !o->inv_std) return false;
+	const ccv_nnc_tensor_t* const params[3] = { o->scale, o->bias ? o->bias : o->dbias, o->dscale };
+	if (!half_shape(o->a, o->mean, params, &o->shape)) return false;
+	const size_t total = tensor_count(o->a->info);
+	if (tensor_count(o->mean->info) != (size_t)o->shape.R || tensor_count(o->inv_std->info) != (size_t)o->shape.R) return false;
+	if ((o->out && tensor_count(o->out->info) != total) || (o->g && tensor_count(o->g->info) != total)) return false;
+	return true;
+}
+static int group_norm_half(EXEC_ARGS)
+{
+	half_ops_t o;
+	if (!half_operands(cmd, inputs, input_size, outputs, output_size, &o)) return CCV_NNC_EXEC_INVALID;
+	const int pt = stat_type(o.inv_std);
+	if (!pt || !dense_of(o.a, CCV_16F) || (o.g && !dense_of(o.g, CCV_16F)) || (o.out && !dense_of(o.out, CCV_16F)) || !dense_of(o.mean, pt) || !dense_of(o.inv_std, pt)) return CCV_NNC_EXEC_INVALID;
+	for (const ccv_nnc_tensor_t* const p : { o.scale, o.bias, (const ccv_nnc_tensor_t*)o.dscale, (const ccv_nnc_tensor_t*)o.dbias })
+		if (p && !dense_of(p, pt)) return CCV_NNC_EXEC_INVALID;
+	gnorm::args_t p = {};
+	p.a = o.a->data.u8; p.g = o.g ? o.g->data.u8 : 0;
+	p.scale = o.scale ? o.scale->data.u8 : 0; p.bias = o.bias ? o.bias->data.u8 : 0;
+	p.out = o.out ? o.out->data.u8 : 0;
+	p.dscale = o.dscale ? o.dscale->data.u8 : 0; p.dbias = o.dbias ? o.dbias->data.u8 : 0;
+	p.epsilon = cmd.info.lnorm.epsilon; // (the quirk at the top of this file)
+	if (cmd.cmd == CCV_NNC_GROUP_NORM_FORWARD) {
+		p.mean = o.mean->data.u8; p.inv_std = o.inv_std->data.u8;
+		return pt == CCV_16F ? gnorm::forward<gnorm::half_t>(p, o.shape, stream_context) : gnorm::forward<float>(p, o.shape, stream_context);
+	}
+	p.mean_in = o.mean->data.u8; p.inv_std_in = o.inv_std->data.u8;
+	return pt == CCV_16F ? gnorm::backward<gnorm::half_t>(p, o.shape, stream_context) : gnorm::backward<float>(p, o.shape, stream_context);
+}
+
 static int _group_norm_forw(EXEC_ARGS)
 {
+	if (input_size >= 1 && is_half(inputs[0])) return group_norm_half(cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
 	if (input_size < 1 || output_size < 3 || !dense_f32(inputs[0]) || !dense_f32(outputs[0]) || !dense_f32(outputs[1]) || !dense_f32(outputs[2])) return CCV_NNC_EXEC_INVALID;
 	const int affine = cmd.info.gnorm.elementwise_affine;
 	const ccv_nnc_tensor_t* scale = affine && input_size >= 2 ? inputs[1] : 0;
@@ -186,6 +285,7 @@ static int _group_norm_forw(EXEC_ARGS)
 }
 static int _group_norm_back(EXEC_ARGS)
 {
+	if (input_size >= 4 && is_half(inputs[3])) return group_norm_half(cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
 	const int affine = cmd.info.gnorm.elementwise_affine;
 	const int im = affine ? 7 : 5, is = affine ? 8 : 6;
 	if (input_size <= is || output_size < 1 || !dense_f32(inputs[0]) || !dense_f32(inputs[3]) || !dense_f32(inputs[im]) || !dense_f32(inputs[is]) || (affine && !dense_f32(inputs[4]))) return CCV_NNC_EXEC_INVALID;
@@ -230,6 +330,13 @@ static int _group_norm_back(EXEC_ARGS)
 }
 
 } // namespace
+
+// half_stage.cpp asks before it leaves the command's half tensors in their own memory (the masks have matched: the tensors they name are dense halves)
+bool nnc::gnorm_half_applies(const ccv_nnc_cmd_t cmd, int, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
+{
+	half_ops_t o;
+	return tune(TUNE_GNORM_HALF_NATIVE) != 0 && half_operands(cmd, inputs, input_size, outputs, output_size, &o);
+}
 
 #define NNC_REG(CMD, BACKEND, EXEC) \
 	extern "C" void _register_command_##CMD##_backend_##BACKEND(ccv_nnc_cmd_backend_registry_t* const registry) \

@@ -276,6 +276,7 @@ enum {
 	TUNE_MUL_PLANES,        // MUL of a dense 4-d activation tensor by a per-(image, channel) vector (squeeze-excite), forward and backward, fp32 and half, on the plane-scale kernels of mul_planes.h (1), or the generic broadcast map / reduce kernels (0)
 	TUNE_OPT_HALF_NATIVE,   // RMSPROP, ADAM, ADAMW and LAMB read and write CCV_16F tensors as halves themselves -- all tensors half, only g half, or only the parameter and state tensors half (optim.h) -- (1), or run on fp32 images of them (0)
 	TUNE_ROW_HALF_NATIVE,   // LAYER_NORM, RMSNORM and plain SOFTMAX, forward and backward, read and write CCV_16F maps as halves themselves on the row kernels of row_ops.h -- every used tensor half, or only the maps -- (1), or run on fp32 images of them (0)
+	TUNE_GNORM_HALF_NATIVE, // GROUP_NORM, forward and backward, reads and writes dense CCV_16F maps in the NCHW-like and NHWC layouts as halves itself on the kernels of group_ops.h -- every used tensor half, or only the maps -- (1), or runs on fp32 images of them (0)
 	TUNE_COUNT
 };
 static_assert(TUNE_GRID_WG_PER_CU == 3, "grid_for() above names this key by value");
@@ -328,6 +329,9 @@ bool mul_planes_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* co
 // cmd_rownorm.cpp / cmd_act_opt.cpp: is this LAYER_NORM / RMSNORM / SOFTMAX command (forward or backward) one the half row kernels (row_ops.h) take -- tuning key,
 // rows x n geometry, n <= ROW_REG_MAX, parameters of n elements or one?  (Types and views are the masks' business in half_stage.cpp.)
 bool rownorm_half_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size);
+// cmd_groupnorm.cpp: is this GROUP_NORM command (forward or backward) one the half kernels of group_ops.h take -- tuning key, one of the two layouts, parameters of
+// exactly C elements on the group axis?  The launcher decides with the same function.
+bool gnorm_half_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size);
 bool softmax_half_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size);
 bool any_half_tensor(ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size);
 int half_to_float(const void* in, float* out, size_t n, ccv_nnc_stream_context_t* ctx);

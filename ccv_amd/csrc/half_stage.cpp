@@ -145,7 +145,7 @@ void warn_refused(const uint32_t cmd, const int ret)
 }
 
 // Rows whose kernels read and write their LARGE tensors in half precision themselves (loads / stores of halves, fp32 arithmetic:
-// cmd_ew.cpp, cmd_norm.cpp, cmd_pool.cpp, cmd_act_opt.cpp, cmd_bcast.cpp's plane-scale MUL, row_ops.h).  Bit i of `in` / `out` = that input / output stays in its own memory when every tensor
+// cmd_ew.cpp, cmd_norm.cpp, cmd_pool.cpp, cmd_act_opt.cpp, cmd_bcast.cpp's plane-scale MUL, row_ops.h, group_ops.h).  Bit i of `in` / `out` = that input / output stays in its own memory when every tensor
 // named by the masks is a dense CCV_16F tensor; the row's small tensors (batch-norm statistics, ...) still get fp32 images.
 static long g_half_staged = 0, g_half_native = 0; // nnc_mi355x_debug_half_counts (test hook; not synchronised: counts, not control)
 // NNC_MI355X_HALF_STATS=1: one line per command at unload -- which rows of a run went through fp32 images of their half tensors (and how many tensors)
@@ -182,6 +182,9 @@ static bool opt_state_native(const ccv_nnc_cmd_t, int, ccv_nnc_tensor_t* const* 
 // row_ops.h: LAYER_NORM (affine and not: the statistics sit in other slots), RMSNORM, SOFTMAX.  The predicates are cmd_rownorm.cpp's / cmd_act_opt.cpp's
 static bool lnorm_affine_native(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size) { return cmd.info.lnorm.elementwise_affine && rownorm_half_applies(cmd, flags, inputs, input_size, outputs, output_size); }
 static bool lnorm_plain_native(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size) { return !cmd.info.lnorm.elementwise_affine && rownorm_half_applies(cmd, flags, inputs, input_size, outputs, output_size); }
+// group_ops.h: GROUP_NORM, the slots of LAYER_NORM.  The predicate is cmd_groupnorm.cpp's
+static bool gnorm_affine_native(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size) { return cmd.info.gnorm.elementwise_affine && gnorm_half_applies(cmd, flags, inputs, input_size, outputs, output_size); }
+static bool gnorm_plain_native(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size) { return !cmd.info.gnorm.elementwise_affine && gnorm_half_applies(cmd, flags, inputs, input_size, outputs, output_size); }
 static const native_half_t g_native_half[] = {
 	{ CCV_NNC_RELU_FORWARD, 1u << 0, 1u << 0 },
 	{ CCV_NNC_RELU_BACKWARD, (1u << 0) | (1u << 2), 1u << 0 },            // g, (a unused), b -> h
@@ -228,6 +231,13 @@ static const native_half_t g_native_half[] = {
 	{ CCV_NNC_LAYER_NORM_BACKWARD, (1u << 0) | (1u << 3) | (1u << 4) | (1u << 7) | (1u << 8), (1u << 0) | (1u << 1) | (1u << 2), lnorm_affine_native }, // g, a, scale, saved_mean, saved_inv_std -> h, dscale, dbias
 	{ CCV_NNC_LAYER_NORM_BACKWARD, (1u << 0) | (1u << 3) | (1u << 5) | (1u << 6), (1u << 0) | (1u << 1) | (1u << 2), lnorm_plain_native },             // g, a, saved_mean, saved_inv_std -> h
 	{ CCV_NNC_LAYER_NORM_BACKWARD, (1u << 0) | (1u << 3), 1u << 0, rownorm_half_applies },
+	// group_ops.h: the same two rows per variant
+	{ CCV_NNC_GROUP_NORM_FORWARD, (1u << 0) | (1u << 1) | (1u << 2), (1u << 0) | (1u << 1) | (1u << 2), gnorm_affine_native }, // a, scale, bias -> b, saved_mean, saved_inv_std
+	{ CCV_NNC_GROUP_NORM_FORWARD, 1u << 0, (1u << 0) | (1u << 1) | (1u << 2), gnorm_plain_native },                            // a -> b, saved_mean, saved_inv_std
+	{ CCV_NNC_GROUP_NORM_FORWARD, 1u << 0, 1u << 0, gnorm_half_applies },
+	{ CCV_NNC_GROUP_NORM_BACKWARD, (1u << 0) | (1u << 3) | (1u << 4) | (1u << 7) | (1u << 8), (1u << 0) | (1u << 1) | (1u << 2), gnorm_affine_native }, // g, a, scale, saved_mean, saved_inv_std -> h, dscale, dbias
+	{ CCV_NNC_GROUP_NORM_BACKWARD, (1u << 0) | (1u << 3) | (1u << 5) | (1u << 6), (1u << 0) | (1u << 1) | (1u << 2), gnorm_plain_native },             // g, a, saved_mean, saved_inv_std -> h
+	{ CCV_NNC_GROUP_NORM_BACKWARD, (1u << 0) | (1u << 3), 1u << 0, gnorm_half_applies },
 	{ CCV_NNC_RMSNORM_FORWARD, (1u << 0) | (1u << 1), (1u << 0) | (1u << 1), rownorm_half_applies },                           // a, scale -> b, saved_inv_std
 	{ CCV_NNC_RMSNORM_FORWARD, 1u << 0, 1u << 0, rownorm_half_applies },
 	{ CCV_NNC_RMSNORM_BACKWARD, (1u << 0) | (1u << 2) | (1u << 3) | (1u << 5), (1u << 0) | (1u << 1), rownorm_half_applies },  // g, a, scale, saved_inv_std -> h, dscale
