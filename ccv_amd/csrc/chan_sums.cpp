@@ -24,6 +24,20 @@ size_t colsum_workspace_bytes(const long rows, const int cols) { return sizeof(f
 // and it is reached (rows = 64 * s0 * s0 gives s0 slices of 64 * s0 rows each), so it is the maximum, not an estimate.
 size_t colsum_workspace_bound(const int cols) { return cols > 0 ? sizeof(float) * (size_t)colsum_slices_most((cols + RC_COLS - 1) / RC_COLS) * (size_t)cols : 0; }
 
+// Slices per plane: none for planes of at most CHAN_RUN_SLICE elements or when the planes alone give CHAN_SLICE_WAVES_PER_CU waves per CU; else as many as
+// that takes, at most ceil(inner / CHAN_RUN_SLICE) of them, each a multiple of eight elements, none empty.
+plane_slices_t chan_plane_slices(const long planes, const long inner)
+{
+	plane_slices_t r = { 1, inner };
+	if (inner <= CHAN_RUN_SLICE || planes < 1) return r;
+	const long want = ((long)device_cu_count() * CHAN_SLICE_WAVES_PER_CU + planes - 1) / planes, most = (inner + CHAN_RUN_SLICE - 1) / CHAN_RUN_SLICE;
+	long slices = want < most ? want : most;
+	if (slices <= 1) return r;
+	r.per = ((inner + slices - 1) / slices + 7) & ~7L;
+	r.slices = (inner + r.per - 1) / r.per;
+	return r;
+}
+
 // The per-image product sums: the tile width among 8, 16, 32, 64 channel vectors that wastes the fewest lanes on the last tile (the widest of equals; fewer than
 // 8 vectors: the next power of two), then pixel slices until the launch has about four workgroups per CU, none with fewer than four pixels per phase.
 scaled_rows_plan_t scaled_rows_plan(const int N, const int cv, const long P)

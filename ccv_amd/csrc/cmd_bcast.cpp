@@ -14,8 +14,10 @@
 //                        (Reductions on the training hot path -- bias gradients, batch-norm statistics -- do NOT come
 //                        through here: they use the two-stage column reducers of cmd_ew.cpp / cmd_norm.cpp.)
 // One pattern of MUL leaves them: an activation tensor times one value per (image, channel), the squeeze-excite scale -- mul_planes.h, mul_planes_plan below.
+// Dense CCV_16F commands of ADD, same-shape MUL, REDUCE_SUM and REDUCE_MEAN whose shapes are flat, a period or runs leave them too: bcast_ops.h (BCAST_HALF_ROUTE).
 #include "common.h"
 #include "mul_planes.h"
+#include "bcast_ops.h"
 #include <math.h>
 
 using namespace nnc;
@@ -232,6 +234,7 @@ static bool f32(const ccv_nnc_tensor_t* t) { return !t || CCV_GET_DATA_TYPE(t->i
 
 static int _add_forw(EXEC_ARGS)
 {
+	BCAST_HALF_ROUTE;
 	if (input_size < 1 || output_size < 1 || !inputs[0] || !outputs[0] || !f32(inputs[0])) return CCV_NNC_EXEC_INVALID;
 	const ccv_nnc_tensor_t* b = input_size > 1 ? inputs[1] : 0;
 	if (!b) { FScale f; f.p = cmd.info.blas.a[0]; return bcast_map(f, inputs[0], 0, outputs[0], stream_context); }
@@ -241,6 +244,7 @@ static int _add_forw(EXEC_ARGS)
 // inputs (g, ...), outputs (da, db): da = p * g, db = q * g, each summed over the axes it was broadcast along; g NULL = ones
 static int _add_back(EXEC_ARGS)
 {
+	BCAST_HALF_ROUTE;
 	const ccv_nnc_tensor_t* g = input_size > 0 ? inputs[0] : 0;
 	const float pq[2] = { cmd.info.blas.a[0], cmd.info.blas.a[1] };
 	for (int i = 0; i < 2 && i < output_size; i++) {
@@ -323,6 +327,7 @@ static int _mul_forw(EXEC_ARGS)
 {
 	mul_plan_t mp;
 	if (mul_planes_plan(cmd, flags, inputs, input_size, outputs, output_size, &mp)) return mp.dt == CCV_16F ? mul_planes_run<half_t>(mp, cmd.info.blas.a[0], stream_context) : mul_planes_run<float>(mp, cmd.info.blas.a[0], stream_context);
+	BCAST_HALF_ROUTE;
 	if (input_size < 1 || output_size < 1 || !inputs[0] || !outputs[0] || !f32(inputs[0])) return CCV_NNC_EXEC_INVALID;
 	const ccv_nnc_tensor_t* b = input_size > 1 ? inputs[1] : 0;
 	if (!b) { FScale f; f.p = cmd.info.blas.a[0]; return bcast_map(f, inputs[0], 0, outputs[0], stream_context); }
@@ -334,6 +339,7 @@ static int _mul_back(EXEC_ARGS)
 {
 	mul_plan_t mp;
 	if (mul_planes_plan(cmd, flags, inputs, input_size, outputs, output_size, &mp)) return mp.dt == CCV_16F ? mul_planes_run<half_t>(mp, cmd.info.blas.a[0], stream_context) : mul_planes_run<float>(mp, cmd.info.blas.a[0], stream_context);
+	BCAST_HALF_ROUTE;
 	if (input_size < 3) return CCV_NNC_EXEC_INVALID;
 	const ccv_nnc_tensor_t* g = inputs[0];
 	const float p = cmd.info.blas.a[0];
@@ -358,12 +364,14 @@ static int _mul_back(EXEC_ARGS)
 
 static int _reduce_sum_forw(EXEC_ARGS)
 {
+	BCAST_HALF_ROUTE;
 	if (input_size < 1 || output_size < 1 || !inputs[0] || !outputs[0] || !f32(inputs[0])) return CCV_NNC_EXEC_INVALID;
 	FCopy f;
 	return bcast_reduce(f, inputs[0], 0, outputs[0], stream_context);
 }
 static int _reduce_sum_back(EXEC_ARGS)
 { // h = g broadcast back to the input shape (reduce_sum_cpu_ref.c:60-117); g NULL = ones
+	BCAST_HALF_ROUTE;
 	if (output_size < 1 || !outputs[0]) return CCV_NNC_EXEC_INVALID;
 	if (input_size < 1 || !inputs[0]) { if (!tensor_contiguous(outputs[0])) return CCV_NNC_EXEC_INVALID; return fill_f32(outputs[0]->data.f32, tensor_count(outputs[0]->info), 1.f, stream_context); }
 	FCopy f;
@@ -371,6 +379,7 @@ static int _reduce_sum_back(EXEC_ARGS)
 }
 static int _reduce_mean_forw(EXEC_ARGS)
 {
+	BCAST_HALF_ROUTE;
 	if (input_size < 1 || output_size < 1 || !inputs[0] || !outputs[0] || !f32(inputs[0])) return CCV_NNC_EXEC_INVALID;
 	const size_t no = tensor_count(outputs[0]->info);
 	FScale f; f.p = no ? 1.f / (float)(tensor_count(inputs[0]->info) / no) : 1.f; // sum of x/count: same order as the reference up to the scaling point
@@ -378,6 +387,7 @@ static int _reduce_mean_forw(EXEC_ARGS)
 }
 static int _reduce_mean_back(EXEC_ARGS)
 {
+	BCAST_HALF_ROUTE;
 	if (output_size < 1 || !outputs[0]) return CCV_NNC_EXEC_INVALID;
 	ccv_nnc_tensor_t* h = outputs[0];
 	const ccv_nnc_tensor_t* g = input_size > 0 ? inputs[0] : 0;
@@ -661,12 +671,31 @@ static int _argmin_forw(EXEC_ARGS) { return argext<false>(cmd, inputs, input_siz
 } // namespace
 
 namespace nnc {
+bool bcast_half_applies(const ccv_nnc_cmd_t cmd, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
+{
+	bcast_plan_t bp;
+	return bcast_half_plan(cmd, flags, inputs, input_size, outputs, output_size, &bp);
+}
+int bcast_half_exec(const ccv_nnc_cmd_t cmd, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const ctx)
+{
+	bcast_plan_t bp;
+	if (!bcast_half_plan(cmd, flags, inputs, input_size, outputs, output_size, &bp)) return BCAST_HALF_NOT_TAKEN;
+	return bcast_half_run(bp, ctx);
+}
 bool mul_planes_applies(const ccv_nnc_cmd_t cmd, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
 {
 	mul_plan_t mp;
 	return mul_planes_plan(cmd, flags, inputs, input_size, outputs, output_size, &mp);
 }
 } // namespace nnc
+
+// Test hook: the form of a pair of shapes as the plan sees it (host arithmetic only, nothing is launched).
+extern "C" int nnc_mi355x_debug_bcast_form(const int big[4], const int small[4], const int sum)
+{
+	nnc::bcast_geom_t g;
+	if (sum) return nnc::bc_same(big, small) ? (nnc::bcast_geom(big, small, &g) ? g.form : 0) : (nnc::bc_sum_geom(big, small, &g) ? g.form : 0);
+	return nnc::bcast_geom(big, small, &g) ? g.form : 0;
+}
 
 
 #define NNC_REG(CMD, BACKEND, FORMATS, DATATYPES, MEMORY, EXEC) \

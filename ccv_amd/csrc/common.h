@@ -277,6 +277,7 @@ enum {
 	TUNE_OPT_HALF_NATIVE,   // RMSPROP, ADAM, ADAMW and LAMB read and write CCV_16F tensors as halves themselves -- all tensors half, only g half, or only the parameter and state tensors half (optim.h) -- (1), or run on fp32 images of them (0)
 	TUNE_ROW_HALF_NATIVE,   // LAYER_NORM, RMSNORM and plain SOFTMAX, forward and backward, read and write CCV_16F maps as halves themselves on the row kernels of row_ops.h -- every used tensor half, or only the maps -- (1), or run on fp32 images of them (0)
 	TUNE_GNORM_HALF_NATIVE, // GROUP_NORM, forward and backward, reads and writes dense CCV_16F maps in the NCHW-like and NHWC layouts as halves itself on the kernels of group_ops.h -- every used tensor half, or only the maps -- (1), or runs on fp32 images of them (0)
+	TUNE_BCAST_HALF_NATIVE, // ADD, same-shape MUL, SCALAR_MUL, REDUCE_SUM and REDUCE_MEAN, forward and backward, read and write dense CCV_16F tensors as halves themselves where the shapes are flat, a period or runs (bcast_ops.h) (1), or run on fp32 images of them (0)
 	TUNE_COUNT
 };
 static_assert(TUNE_GRID_WG_PER_CU == 3, "grid_for() above names this key by value");
@@ -332,6 +333,13 @@ bool rownorm_half_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* 
 // cmd_groupnorm.cpp: is this GROUP_NORM command (forward or backward) one the half kernels of group_ops.h take -- tuning key, one of the two layouts, parameters of
 // exactly C elements on the group axis?  The launcher decides with the same function.
 bool gnorm_half_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size);
+// cmd_bcast.cpp / cmd_ew.cpp: is this ADD / MUL / REDUCE_SUM / REDUCE_MEAN / SCALAR_MUL command (forward or backward) one the half kernels of bcast_ops.h take -- tuning key,
+// every used tensor a dense CCV_16F one, shapes that are flat, a period or runs (bcast_half_plan)?  The exec functions decide with the same plan.
+bool bcast_half_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size);
+constexpr int BCAST_HALF_NOT_TAKEN = 1; // bcast_half_exec: the command is not one of bcast_ops.h's, nothing was launched (else what the native kernels returned, CCV_NNC_EXEC_*)
+int bcast_half_exec(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size, ccv_nnc_stream_context_t* ctx);
+// at the top of an exec function with the usual parameter names: bcast_ops.h takes the command (dense halves, shapes it knows) or leaves it to the code below
+#define BCAST_HALF_ROUTE do { const int taken = nnc::bcast_half_exec(cmd, flags, inputs, input_size, outputs, output_size, stream_context); if (taken != nnc::BCAST_HALF_NOT_TAKEN) return taken; } while (0)
 bool softmax_half_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size);
 bool any_half_tensor(ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size);
 int half_to_float(const void* in, float* out, size_t n, ccv_nnc_stream_context_t* ctx);

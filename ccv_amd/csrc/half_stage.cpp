@@ -145,7 +145,7 @@ void warn_refused(const uint32_t cmd, const int ret)
 }
 
 // Rows whose kernels read and write their LARGE tensors in half precision themselves (loads / stores of halves, fp32 arithmetic:
-// cmd_ew.cpp, cmd_norm.cpp, cmd_pool.cpp, cmd_act_opt.cpp, cmd_bcast.cpp's plane-scale MUL, row_ops.h, group_ops.h).  Bit i of `in` / `out` = that input / output stays in its own memory when every tensor
+// cmd_ew.cpp, cmd_norm.cpp, cmd_pool.cpp, cmd_act_opt.cpp, cmd_bcast.cpp's plane-scale MUL, row_ops.h, group_ops.h, bcast_ops.h).  Bit i of `in` / `out` = that input / output stays in its own memory when every tensor
 // named by the masks is a dense CCV_16F tensor; the row's small tensors (batch-norm statistics, ...) still get fp32 images.
 static long g_half_staged = 0, g_half_native = 0; // nnc_mi355x_debug_half_counts (test hook; not synchronised: counts, not control)
 // NNC_MI355X_HALF_STATS=1: one line per command at unload -- which rows of a run went through fp32 images of their half tensors (and how many tensors)
@@ -215,6 +215,17 @@ static const native_half_t g_native_half[] = {
 	// cmd_bcast.cpp: only the squeeze-excite pattern of mul_planes.h; every other MUL runs on fp32 images
 	{ CCV_NNC_MUL_FORWARD, (1u << 0) | (1u << 1), 1u << 0, mul_planes_applies },            // a, b -> c
 	{ CCV_NNC_MUL_BACKWARD, (1u << 0) | (1u << 1) | (1u << 2), (1u << 0) | (1u << 1), mul_planes_applies }, // g, a, b -> da, db
+	// bcast_ops.h: ADD, same-shape MUL (behind the plane-scale rows), REDUCE_SUM / REDUCE_MEAN and SCALAR_MUL where bcast_half_plan takes the shapes (flat, a period, runs)
+	{ CCV_NNC_MUL_FORWARD, (1u << 0) | (1u << 1), 1u << 0, bcast_half_applies },
+	{ CCV_NNC_MUL_BACKWARD, (1u << 0) | (1u << 1) | (1u << 2), (1u << 0) | (1u << 1), bcast_half_applies },
+	{ CCV_NNC_ADD_FORWARD, (1u << 0) | (1u << 1), 1u << 0, bcast_half_applies },             // a, b -> c
+	{ CCV_NNC_ADD_BACKWARD, 1u << 0, (1u << 0) | (1u << 1), bcast_half_applies },            // g -> da, db
+	{ CCV_NNC_REDUCE_SUM_FORWARD, 1u << 0, 1u << 0, bcast_half_applies },                    // a -> b
+	{ CCV_NNC_REDUCE_SUM_BACKWARD, 1u << 0, 1u << 0, bcast_half_applies },                   // g -> h
+	{ CCV_NNC_REDUCE_MEAN_FORWARD, 1u << 0, 1u << 0, bcast_half_applies },
+	{ CCV_NNC_REDUCE_MEAN_BACKWARD, 1u << 0, 1u << 0, bcast_half_applies },
+	{ CCV_NNC_SCALAR_MUL_FORWARD, 1u << 0, 1u << 0, bcast_half_applies },                    // a -> b (cmd_ew.cpp)
+	{ CCV_NNC_SCALAR_MUL_BACKWARD, 1u << 0, 1u << 0, bcast_half_applies },                   // g -> h
 	// optim.h: g, a, m, v[, vm] -> b, n, u[, um].  Three rows per command, tried in order: every tensor half; g alone (half gradients into fp32 master
 	// parameters); the parameter and state tensors alone (fp32 gradients)
 #define OPT_ROWS(CMD) { CMD, OPT_G | OPT_STATE_IN, OPT_STATE_OUT, opt_native }, { CMD, OPT_G, 0, opt_g_native }, { CMD, OPT_STATE_IN, OPT_STATE_OUT, opt_state_native }

@@ -479,6 +479,9 @@ long nnc_mi355x_debug_bn_cluster_launches(void);
 /* Test hook for the column sums (chan_sums.cpp), host arithmetic only: the slice plan of a rows x cols sum, the workspace bytes that call requests, and
  * the most any call with `cols` columns requests -- the head size of callers that keep data of their own behind the partials. */
 void nnc_mi355x_debug_colsum_plan(long rows, int cols, long* slices, long* rows_per_slice, size_t* bytes, size_t* bound);
+/* Test hook for the half broadcast rows (bcast_ops.h), host arithmetic only: the form the plan gives a pair of shapes right-aligned to four axes -- 0 refused,
+ * 1 flat, 2 period, 3 run -- for a map (sum == 0) or a sum (sum != 0: the per-image sums of the period form take at most 65 535 images). */
+int nnc_mi355x_debug_bcast_form(const int big[4], const int small[4], int sum);
 /* commands that have reached an exec function of this library since it was loaded (tools/host_resnet_bench.c divides the host's enqueue time by it) */
 long nnc_mi355x_debug_exec_count(void);
 /* Test hook for the CCV_16F datapath (half_stage.cpp): how many half-precision tensors have been given an fp32 image so far
