@@ -7,41 +7,12 @@
 // Every coefficient is recomputed per thread with the reference's exact mixed float / double expression, so the taps agree bit for bit.
 // Backward is a GATHER: one thread per input-gradient element walks the (few) outputs that reference it in (yd, xd, tap) order -- the order
 // the reference's sequential scatter adds them -- so sums are bit-identical without atomics.  HBM-bound, 4 bytes per lane.
-#include "common.h"
+#include "upsample_ops.h" // UpGeom, nearest_src, bi_coeff, upsample_geometry; the half kernels and their plan
 
 using namespace nnc;
 
 namespace {
 
-enum { UPSAMPLE_NEAREST = 0, UPSAMPLE_BILINEAR = 1 };
-
-struct UpGeom {
-	int N, C, AH, AW, BH, BW;      // a = the small (source) image, b = the resampled one
-	long an, ac, ah, aw;           // element strides of a for (n, c, y, x)
-	long bn, bc, bh, bw;
-	float rh, rw;
-	int align, nchw;
-};
-
-__device__ __forceinline__ int nearest_src(const int d, const float r, const int A, const int align)
-{
-#pragma clang fp contract(off)
-	const int s = align ? (int)((double)((float)d * r) + 0.5) : (int)(((double)d + 0.5) * (double)r);
-	return s < A - 1 ? s : A - 1;
-}
-struct Bi { int si0, si1; float sc0, sc1; };
-__device__ __forceinline__ Bi bi_coeff(const int i, const float s, const int A, const int align)
-{
-#pragma clang fp contract(off)
-	Bi c;
-	const float xs = align ? (float)i * s : (float)(((double)i + 0.5) * (double)s - 0.5);
-	c.si0 = (int)xs;
-	const int t = (int)(xs + 1.f);
-	c.si1 = t < A - 1 ? t : A - 1;
-	c.sc1 = xs - (float)c.si0;
-	c.sc0 = (float)(1.0 - (double)c.sc1);
-	return c;
-}
 __device__ __forceinline__ void split4(size_t idx, const int d1, const int d2, const int d3, int& i0, int& i1, int& i2, int& i3)
 {
 	i3 = (int)(idx % d3); idx /= d3;
@@ -130,60 +101,82 @@ __global__ void __launch_bounds__(256) upsample_back_kernel(const UpGeom g, cons
 
 static bool dense_f32(const ccv_nnc_tensor_t* t) { return t && tensor_contiguous(t) && CCV_GET_DATA_TYPE(t->info.datatype) == CCV_32F; }
 
-// small = source-resolution tensor (forward input / backward output), big = resampled tensor
-static bool geometry(const ccv_nnc_cmd_t& cmd, const ccv_nnc_tensor_t* small, const ccv_nnc_tensor_t* big, UpGeom* g)
+#define EXEC_ARGS const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context
+
+// the fp32 launch record: "upsample_forw|nnc::upsample_forw_kernel" / "upsample_back|nnc::upsample_back_kernel" (the half route through fp32 images files it too)
+static int upsample_f32(const bool forward, const int type, const UpGeom& g, const float* in, float* out, const size_t total, ccv_nnc_stream_context_t* ctx)
 {
-	if (small->info.format != big->info.format) return false;
-	const int nd = tensor_nd(small->info.dim);
-	if (nd != tensor_nd(big->info.dim) || nd < 3 || nd > 4) return false;
-	int ad[4], bd[4];
-	for (int k = 0; k < 4; k++) { const int j = k - (4 - nd); ad[k] = j >= 0 ? small->info.dim[j] : 1; bd[k] = j >= 0 ? big->info.dim[j] : 1; }
-	g->nchw = small->info.format == CCV_TENSOR_FORMAT_NCHW;
-	if (g->nchw) { g->N = ad[0]; g->C = ad[1]; g->AH = ad[2]; g->AW = ad[3]; g->BH = bd[2]; g->BW = bd[3]; if (bd[0] != ad[0] || bd[1] != ad[1]) return false; }
-	else { g->N = ad[0]; g->AH = ad[1]; g->AW = ad[2]; g->C = ad[3]; g->BH = bd[1]; g->BW = bd[2]; if (bd[0] != ad[0] || bd[3] != ad[3]) return false; }
-	if (g->AH < 1 || g->AW < 1 || g->BH < 1 || g->BW < 1) return false;
-	if (g->nchw) { g->aw = 1; g->ah = g->AW; g->ac = (long)g->AH * g->AW; g->an = g->ac * g->C; g->bw = 1; g->bh = g->BW; g->bc = (long)g->BH * g->BW; g->bn = g->bc * g->C; }
-	else { g->ac = 1; g->aw = g->C; g->ah = (long)g->AW * g->C; g->an = g->ah * g->AH; g->bc = 1; g->bw = g->C; g->bh = (long)g->BW * g->C; g->bn = g->bh * g->BH; }
-	g->align = cmd.info.upsample.align_corners;
-	g->rh = g->align ? (float)(g->AH - 1) / (float)(g->BH - 1 > 1 ? g->BH - 1 : 1) : (float)g->AH / (float)g->BH;
-	g->rw = g->align ? (float)(g->AW - 1) / (float)(g->BW - 1 > 1 ? g->BW - 1 : 1) : (float)g->AW / (float)g->BW;
+	hipStream_t stream = stream_of(ctx);
+	const double na = (double)g.N * g.C * g.AH * g.AW, nb = (double)g.N * g.C * g.BH * g.BW;
+	note_kernel(forward ? "upsample_forw" : "upsample_back");
+	ProfScope prof(forward ? "upsample_forw|nnc::upsample_forw_kernel" : "upsample_back|nnc::upsample_back_kernel", forward ? nb : na, sizeof(float) * (na + nb), g.N, g.C, g.BH, g.BW, 1, stream);
+	const dim3 grid(grid_for(total, 256));
+	if (forward && type == UPSAMPLE_NEAREST) hipLaunchKernelGGL(HIP_KERNEL_NAME(upsample_forw_kernel<UPSAMPLE_NEAREST>), grid, dim3(256), 0, stream, g, in, out, total);
+	else if (forward) hipLaunchKernelGGL(HIP_KERNEL_NAME(upsample_forw_kernel<UPSAMPLE_BILINEAR>), grid, dim3(256), 0, stream, g, in, out, total);
+	else if (type == UPSAMPLE_NEAREST) hipLaunchKernelGGL(HIP_KERNEL_NAME(upsample_back_kernel<UPSAMPLE_NEAREST>), grid, dim3(256), 0, stream, g, in, out, total);
+	else hipLaunchKernelGGL(HIP_KERNEL_NAME(upsample_back_kernel<UPSAMPLE_BILINEAR>), grid, dim3(256), 0, stream, g, in, out, total);
+	HIP_ENFORCE(hipGetLastError());
+	return CCV_NNC_EXEC_SUCCESS;
+}
+// dense halves in a geometry upsample_ops.h takes: its kernels; everything else: the code below, as before
+static bool upsample_half_route(const ccv_nnc_cmd_t cmd, const int flags, const ccv_nnc_tensor_t* small, const ccv_nnc_tensor_t* big, const bool forward, ccv_nnc_stream_context_t* ctx, int* ret)
+{
+	upsample_plan_t up;
+	if (!small || !big || !upsample_half_plan(cmd, flags, small, big, &up)) return false;
+	*ret = upsample_half_run(up, forward, ctx);
 	return true;
 }
 
-#define EXEC_ARGS const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context
-
 static int _upsample_forw(EXEC_ARGS)
 {
+	int ret;
+	if (input_size >= 1 && output_size >= 1 && upsample_half_route(cmd, flags, inputs[0], outputs[0], true, stream_context, &ret)) return ret;
 	if (input_size < 1 || output_size < 1 || !dense_f32(inputs[0]) || !dense_f32(outputs[0])) return CCV_NNC_EXEC_INVALID;
 	UpGeom g;
-	if (!geometry(cmd, inputs[0], outputs[0], &g)) return CCV_NNC_EXEC_INVALID;
+	if (!upsample_geometry(cmd, inputs[0], outputs[0], &g)) return CCV_NNC_EXEC_INVALID;
 	const int type = cmd.info.upsample.type;
 	if (g.rh > 1.f || g.rw > 1.f) return CCV_NNC_EXEC_INVALID; // enlargement only: the reference asserts the same in every variant (:44-45, :273-274)
 	const size_t total = tensor_count(outputs[0]->info);
 	if (total == 0) return CCV_NNC_EXEC_SUCCESS;
-	if (type == UPSAMPLE_NEAREST) hipLaunchKernelGGL(HIP_KERNEL_NAME(upsample_forw_kernel<UPSAMPLE_NEAREST>), dim3(grid_for(total, 256)), dim3(256), 0, stream_of(stream_context), g, (const float*)inputs[0]->data.f32, outputs[0]->data.f32, total);
-	else if (type == UPSAMPLE_BILINEAR) hipLaunchKernelGGL(HIP_KERNEL_NAME(upsample_forw_kernel<UPSAMPLE_BILINEAR>), dim3(grid_for(total, 256)), dim3(256), 0, stream_of(stream_context), g, (const float*)inputs[0]->data.f32, outputs[0]->data.f32, total);
-	else return CCV_NNC_EXEC_INVALID;
-	HIP_ENFORCE(hipGetLastError());
-	return CCV_NNC_EXEC_SUCCESS;
+	if (type != UPSAMPLE_NEAREST && type != UPSAMPLE_BILINEAR) return CCV_NNC_EXEC_INVALID;
+	return upsample_f32(true, type, g, (const float*)inputs[0]->data.f32, outputs[0]->data.f32, total, stream_context);
 }
 static int _upsample_back(EXEC_ARGS)
 { // inputs[0] = gradient at the resampled resolution -> outputs[0] = gradient at the source resolution
+	int ret;
+	if (input_size >= 1 && output_size >= 1 && upsample_half_route(cmd, flags, outputs[0], inputs[0], false, stream_context, &ret)) return ret;
 	if (input_size < 1 || output_size < 1 || !dense_f32(inputs[0]) || !dense_f32(outputs[0])) return CCV_NNC_EXEC_INVALID;
 	UpGeom g;
-	if (!geometry(cmd, outputs[0], inputs[0], &g)) return CCV_NNC_EXEC_INVALID;
+	if (!upsample_geometry(cmd, outputs[0], inputs[0], &g)) return CCV_NNC_EXEC_INVALID;
 	const int type = cmd.info.upsample.type;
 	if (g.rh > 1.f || g.rw > 1.f) return CCV_NNC_EXEC_INVALID;
 	const size_t total = tensor_count(outputs[0]->info);
 	if (total == 0) return CCV_NNC_EXEC_SUCCESS;
-	if (type == UPSAMPLE_NEAREST) hipLaunchKernelGGL(HIP_KERNEL_NAME(upsample_back_kernel<UPSAMPLE_NEAREST>), dim3(grid_for(total, 256)), dim3(256), 0, stream_of(stream_context), g, (const float*)inputs[0]->data.f32, outputs[0]->data.f32, total);
-	else if (type == UPSAMPLE_BILINEAR) hipLaunchKernelGGL(HIP_KERNEL_NAME(upsample_back_kernel<UPSAMPLE_BILINEAR>), dim3(grid_for(total, 256)), dim3(256), 0, stream_of(stream_context), g, (const float*)inputs[0]->data.f32, outputs[0]->data.f32, total);
-	else return CCV_NNC_EXEC_INVALID;
-	HIP_ENFORCE(hipGetLastError());
-	return CCV_NNC_EXEC_SUCCESS;
+	if (type != UPSAMPLE_NEAREST && type != UPSAMPLE_BILINEAR) return CCV_NNC_EXEC_INVALID;
+	return upsample_f32(false, type, g, (const float*)inputs[0]->data.f32, outputs[0]->data.f32, total, stream_context);
 }
 
 } // namespace
+
+namespace nnc {
+bool upsample_half_applies(const ccv_nnc_cmd_t cmd, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
+{
+	if (input_size < 1 || output_size < 1 || !inputs[0] || !outputs[0]) return false;
+	const bool forward = cmd.cmd == CCV_NNC_UPSAMPLE_FORWARD;
+	upsample_plan_t up;
+	return upsample_half_plan(cmd, flags, forward ? inputs[0] : outputs[0], forward ? outputs[0] : inputs[0], &up);
+}
+} // namespace nnc
+
+// Test hook: what the plan makes of a geometry (host arithmetic only, nothing is launched): 0 refused, else the vector width of the forward instance on
+// 16-byte-aligned bases plus 16 times that of the backward one.  dims: N, C, AH, AW, BH, BW.
+extern "C" int nnc_mi355x_debug_upsample_plan(const int nchw, const int dims[6], const int type, const int align_corners)
+{
+	nnc::upsample_plan_t up;
+	if (!nnc::up_geom_fill(&up.g, nchw, dims[0], dims[1], dims[2], dims[3], dims[4], dims[5], align_corners) || !nnc::up_geom_native(up.g, type)) return 0;
+	up.type = type; up.small = 0; up.big = 0;
+	return nnc::up_vector_width(up, true) + 16 * nnc::up_vector_width(up, false);
+}
 
 #define NNC_REG(CMD, BACKEND, EXEC) \
 	extern "C" void _register_command_##CMD##_backend_##BACKEND(ccv_nnc_cmd_backend_registry_t* const registry) \

@@ -278,6 +278,7 @@ enum {
 	TUNE_ROW_HALF_NATIVE,   // LAYER_NORM, RMSNORM and plain SOFTMAX, forward and backward, read and write CCV_16F maps as halves themselves on the row kernels of row_ops.h -- every used tensor half, or only the maps -- (1), or run on fp32 images of them (0)
 	TUNE_GNORM_HALF_NATIVE, // GROUP_NORM, forward and backward, reads and writes dense CCV_16F maps in the NCHW-like and NHWC layouts as halves itself on the kernels of group_ops.h -- every used tensor half, or only the maps -- (1), or runs on fp32 images of them (0)
 	TUNE_BCAST_HALF_NATIVE, // ADD, same-shape MUL, SCALAR_MUL, REDUCE_SUM and REDUCE_MEAN, forward and backward, read and write dense CCV_16F tensors as halves themselves where the shapes are flat, a period or runs (bcast_ops.h) (1), or run on fp32 images of them (0)
+	TUNE_UPSAMPLE_HALF_NATIVE, // UPSAMPLE_FORWARD / UPSAMPLE_BACKWARD (nearest and bilinear, align_corners or not) read and write dense CCV_16F tensors in the NCHW and NHWC layouts as halves themselves on the kernels of upsample_ops.h (1), or run on fp32 images of them (0); 2 = as 1 on the scalar instances everywhere (measurements)
 	TUNE_COUNT
 };
 static_assert(TUNE_GRID_WG_PER_CU == 3, "grid_for() above names this key by value");
@@ -340,6 +341,9 @@ constexpr int BCAST_HALF_NOT_TAKEN = 1; // bcast_half_exec: the command is not o
 int bcast_half_exec(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size, ccv_nnc_stream_context_t* ctx);
 // at the top of an exec function with the usual parameter names: bcast_ops.h takes the command (dense halves, shapes it knows) or leaves it to the code below
 #define BCAST_HALF_ROUTE do { const int taken = nnc::bcast_half_exec(cmd, flags, inputs, input_size, outputs, output_size, stream_context); if (taken != nnc::BCAST_HALF_NOT_TAKEN) return taken; } while (0)
+// cmd_upsample.cpp: is this UPSAMPLE_FORWARD / UPSAMPLE_BACKWARD command one the half kernels of upsample_ops.h take -- tuning key, no accumulation, both tensors dense
+// CCV_16F ones with memory of their own, an enlargement by a non-zero ratio, fewer than 2^31 elements (upsample_half_plan)?  The exec functions decide with the same plan.
+bool upsample_half_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size);
 bool softmax_half_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size);
 bool any_half_tensor(ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size);
 int half_to_float(const void* in, float* out, size_t n, ccv_nnc_stream_context_t* ctx);

@@ -482,6 +482,11 @@ void nnc_mi355x_debug_colsum_plan(long rows, int cols, long* slices, long* rows_
 /* Test hook for the half broadcast rows (bcast_ops.h), host arithmetic only: the form the plan gives a pair of shapes right-aligned to four axes -- 0 refused,
  * 1 flat, 2 period, 3 run -- for a map (sum == 0) or a sum (sum != 0: the per-image sums of the period form take at most 65 535 images). */
 int nnc_mi355x_debug_bcast_form(const int big[4], const int small[4], int sum);
+/* Test hook for the half upsample rows (upsample_ops.h; NNC_MI355X_UPSAMPLE_HALF_NATIVE=0 / nnc_mi355x_tune_set("UPSAMPLE_HALF_NATIVE", 0) puts UPSAMPLE_FORWARD /
+ * BACKWARD on CCV_16F tensors back on fp32 images), host arithmetic only: what the plan makes of dense tensors of these extents (dims: N, C, AH, AW, BH, BW;
+ * A the source, B the resampled map) -- 0 refused (a type other than 0 / 1, a ratio above 1 or of 0, 2^31 elements or more), else the vector width (8 or 1) of the
+ * forward instance on 16-byte-aligned bases plus 16 times that of the backward one. */
+int nnc_mi355x_debug_upsample_plan(int nchw, const int dims[6], int type, int align_corners);
 /* commands that have reached an exec function of this library since it was loaded (tools/host_resnet_bench.c divides the host's enqueue time by it) */
 long nnc_mi355x_debug_exec_count(void);
 /* Test hook for the CCV_16F datapath (half_stage.cpp): how many half-precision tensors have been given an fp32 image so far
