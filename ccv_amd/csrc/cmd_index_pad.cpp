@@ -4,27 +4,15 @@
 //                 interpolate between rows j and j+1); backward h = 0, then h[indices[i]][:] += g[i][:] in row order
 //   pad           lib/nnc/cmd/pad/ccv_nnc_pad_cpu_ref.c:13-140              begin = cmd.info.size.dim[], end = cmd.info.pad.end[]
 // Both are HBM-bound copies.  The scatter-add keeps the reference's summation order (rows visited in order per column) so that
-// repeated indices give bit-identical sums: one thread per column walks the rows; columns are the parallel dimension.
-#include "common.h"
+// repeated indices give bit-identical sums.  Dense tensors (fp32 and half; index_ops.h, tunable INDEX_BACK_TILES): a wave per tile of destination rows
+// and columns walks the sources that name its rows in order, accumulators in LDS, and writes the tile once.  Views and the key at 0: one thread per column walks
+// the rows; columns are the parallel dimension.
+// Dense CCV_16F tensors run on the kernels of index_ops.h as halves (tunable INDEX_PAD_HALF_NATIVE); everything else in half precision runs on fp32 images.
+#include "index_ops.h" // index_lerp, the pad kernels; the half kernels, the tile scatter-add and their plans
 
 using namespace nnc;
 
 namespace {
-
-struct dims4_t { int d[4]; long s[4]; };
-static bool dims4(const ccv_nnc_tensor_t* t, dims4_t* o)
-{ // dims right-aligned to 4 with element strides
-	const int nd = tensor_nd(t->info.dim);
-	if (nd > 4) return false;
-	int st[CCV_NNC_MAX_DIM_ALLOC];
-	tensor_strides(t, st);
-	for (int k = 0; k < 4; k++) {
-		const int j = k - (4 - nd);
-		o->d[k] = j >= 0 ? t->info.dim[j] : 1;
-		o->s[k] = j >= 0 ? st[j] : 0;
-	}
-	return true;
-}
 
 // ---- index select -----------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) index_select_i32_kernel(const float* a, const int* idx, float* b, const int rows, const int cols, const long a_inc, const long b_inc)
@@ -40,11 +28,8 @@ __global__ void __launch_bounds__(256) index_select_f32_kernel(const float* a, c
 	const size_t n = (size_t)rows * cols, stride = (size_t)gridDim.x * blockDim.x;
 	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
 		const size_t r = i / cols, c = i - r * cols;
-		const float f = idx[r];
-		const int j0 = (int)f;
-		const int j1 = j0 + 1 < a_rows - 1 ? j0 + 1 : a_rows - 1;
-		const float w1 = f - j0, w0 = 1.f - w1;
-		b[r * b_inc + c] = a[(long)j0 * a_inc + c] * w0 + a[(long)j1 * a_inc + c] * w1;
+		const IdxLerp k = index_lerp_rows(idx[r], a_rows);
+		b[r * b_inc + c] = index_lerp(a[(long)k.j0 * a_inc + c], a[(long)k.j1 * a_inc + c], k);
 	}
 }
 __global__ void __launch_bounds__(256) index_scatter_add_kernel(const float* g, const int* idx, float* h, const int g_rows, const int cols, const long g_inc, const long h_inc)
@@ -74,6 +59,8 @@ static void rows_cols(const ccv_nnc_tensor_t* t, int* rows, int* cols, long* inc
 static int _index_select_forw(EXEC_ARGS)
 {
 	if (input_size < 2 || output_size < 1 || !inputs[0] || !inputs[1] || !outputs[0]) return CCV_NNC_EXEC_INVALID;
+	index_plan_t ip;
+	if (index_half_plan(true, flags, inputs[0], outputs[0], inputs[1], &ip)) return index_gather_run(ip, stream_context); // dense halves: index_ops.h
 	const ccv_nnc_tensor_t* a = inputs[0];
 	const ccv_nnc_tensor_t* ind = inputs[1];
 	ccv_nnc_tensor_t* b = outputs[0];
@@ -99,105 +86,85 @@ static int _index_select_back(EXEC_ARGS)
 	const ccv_nnc_tensor_t* g = inputs[0];
 	const ccv_nnc_tensor_t* ind = inputs[2];
 	ccv_nnc_tensor_t* h = outputs[0];
+	hipStream_t stream = stream_of(stream_context);
+	index_plan_t ip;
+	const bool half = index_half_plan(false, flags, h, g, ind, &ip);
+	if (half || index_back_plan(flags, h, g, ind, &ip)) { // dense tensors: the tile kernel zeroes and sums in one launch (index_ops.h)
+		if (output_size >= 2 && outputs[1] && tensor_contiguous(outputs[1])) HIP_ENFORCE(hipMemsetAsync(outputs[1]->data.u8, 0, tensor_count(outputs[1]->info) * datatype_size(CCV_GET_DATA_TYPE(outputs[1]->info.datatype)), stream));
+		return half ? index_scatter_run<half_t>(ip, stream_context) : index_scatter_run<float>(ip, stream_context);
+	}
 	if (CCV_GET_DATA_TYPE(g->info.datatype) != CCV_32F || CCV_GET_DATA_TYPE(ind->info.datatype) != CCV_32S || tensor_nd(g->info.dim) > 2 || tensor_nd(h->info.dim) > 2 || !tensor_contiguous(ind)) return CCV_NNC_EXEC_INVALID;
 	int g_rows, g_cols, h_rows, h_cols;
 	long g_inc, h_inc;
 	rows_cols(g, &g_rows, &g_cols, &g_inc);
 	rows_cols(h, &h_rows, &h_cols, &h_inc);
 	if (g_cols != h_cols || tensor_count(ind->info) != (size_t)g_rows) return CCV_NNC_EXEC_INVALID;
-	hipStream_t stream = stream_of(stream_context);
 	if (h_rows > 0 && h_cols > 0) hipLaunchKernelGGL(zero_rows_kernel, dim3(grid_for((size_t)h_rows * h_cols, 256)), dim3(256), 0, stream, h->data.f32, h_rows, h_cols, h_inc);
 	if (output_size >= 2 && outputs[1] && tensor_contiguous(outputs[1])) HIP_ENFORCE(hipMemsetAsync(outputs[1]->data.u8, 0, tensor_count(outputs[1]->info) * datatype_size(CCV_GET_DATA_TYPE(outputs[1]->info.datatype)), stream));
-	if (g_rows > 0 && g_cols > 0) hipLaunchKernelGGL(index_scatter_add_kernel, dim3((g_cols + 255) / 256), dim3(256), 0, stream, (const float*)g->data.f32, (const int*)ind->data.i32, h->data.f32, g_rows, g_cols, g_inc, h_inc);
+	if (g_rows > 0 && g_cols > 0) {
+		note_kernel("index_scatter_add");
+		ProfScope prof("index_select_back|nnc::index_scatter_add_kernel", (double)g_rows * g_cols, sizeof(float) * 3.0 * g_rows * g_cols, g_rows, g_cols, h_rows, 1, 1, stream);
+		hipLaunchKernelGGL(index_scatter_add_kernel, dim3((g_cols + 255) / 256), dim3(256), 0, stream, (const float*)g->data.f32, (const int*)ind->data.i32, h->data.f32, g_rows, g_cols, g_inc, h_inc);
+	}
 	HIP_ENFORCE(hipGetLastError());
 	return CCV_NNC_EXEC_SUCCESS;
 }
 
 // ---- pad ----------------------------------------------------------------------------------------------------------------------------
-enum { PAD_ZERO = 0, PAD_REPLICATE = 1 }; // CCV_NNC_PAD_* (ccv_nnc.h:98-99)
-struct pad_args_t { int bd[4]; int ad[4]; int begin[4]; long sa[4], sb[4]; };
-template <int TYPE>
-__global__ void __launch_bounds__(256) pad_forw_kernel(const float* a, float* b, const pad_args_t m, const size_t n)
+// the kernels and pad_args_fill: index_ops.h.  Dense halves run there; fp32 tensors and views below
+static bool pad_half_route(const ccv_nnc_cmd_t cmd, const int flags, const ccv_nnc_tensor_t* small, const ccv_nnc_tensor_t* big, const bool forward, ccv_nnc_stream_context_t* ctx, int* ret)
 {
-	const size_t stride = (size_t)gridDim.x * blockDim.x;
-	for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += stride) {
-		size_t r = idx;
-		int i[4];
-		i[3] = (int)(r % m.bd[3]); r /= m.bd[3];
-		i[2] = (int)(r % m.bd[2]); r /= m.bd[2];
-		i[1] = (int)(r % m.bd[1]); r /= m.bd[1];
-		i[0] = (int)r;
-		long ao = 0, bo = 0;
-		bool inside = true;
-#pragma unroll
-		for (int k = 0; k < 4; k++) {
-			int j = i[k] - m.begin[k];
-			if (TYPE == PAD_REPLICATE) j = j < 0 ? 0 : (j > m.ad[k] - 1 ? m.ad[k] - 1 : j);
-			else inside = inside & (j >= 0) & (j < m.ad[k]);
-			ao += (long)j * m.sa[k];
-			bo += (long)i[k] * m.sb[k];
-		}
-		b[bo] = (TYPE == PAD_REPLICATE || inside) ? a[inside ? ao : 0] : 0.f;
-	}
-}
-// h[i] = g[i + begin]
-__global__ void __launch_bounds__(256) pad_back_kernel(const float* g, float* h, const pad_args_t m, const size_t n)
-{
-	const size_t stride = (size_t)gridDim.x * blockDim.x;
-	for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += stride) {
-		size_t r = idx;
-		int i[4];
-		i[3] = (int)(r % m.ad[3]); r /= m.ad[3];
-		i[2] = (int)(r % m.ad[2]); r /= m.ad[2];
-		i[1] = (int)(r % m.ad[1]); r /= m.ad[1];
-		i[0] = (int)r;
-		long go = 0, ho = 0;
-#pragma unroll
-		for (int k = 0; k < 4; k++) { go += (long)(i[k] + m.begin[k]) * m.sb[k]; ho += (long)i[k] * m.sa[k]; }
-		h[ho] = g[go];
-	}
-}
-// small = the unpadded tensor (a / h), big = the padded one (b / g)
-static int pad_args(const ccv_nnc_cmd_t& cmd, const ccv_nnc_tensor_t* small, const ccv_nnc_tensor_t* big, pad_args_t* m)
-{
-	dims4_t ss, sb;
-	if (!dims4(small, &ss) || !dims4(big, &sb)) return 0;
-	const int nd = tensor_nd(small->info.dim), offset = 4 - nd;
-	for (int k = 0; k < 4; k++) {
-		const int x = k - offset;
-		m->begin[k] = x >= 0 ? cmd.info.size.dim[x] : 0;
-		const int end = x >= 0 ? cmd.info.pad.end[x] : 0;
-		if (m->begin[k] < 0 || end < 0 || sb.d[k] != ss.d[k] + m->begin[k] + end) return 0;
-		m->ad[k] = ss.d[k]; m->bd[k] = sb.d[k]; m->sa[k] = ss.s[k]; m->sb[k] = sb.s[k];
-	}
-	return 1;
+	pad_plan_t pp;
+	if (!small || !big || !pad_half_plan(cmd, flags, small, big, forward, &pp)) return false;
+	*ret = pad_half_run(pp, forward, ctx);
+	return true;
 }
 static int _pad_forw(EXEC_ARGS)
 {
+	int ret;
+	if (input_size >= 1 && output_size >= 1 && pad_half_route(cmd, flags, inputs[0], outputs[0], true, stream_context, &ret)) return ret;
 	if (input_size < 1 || output_size < 1 || !inputs[0] || !outputs[0] || CCV_GET_DATA_TYPE(inputs[0]->info.datatype) != CCV_32F) return CCV_NNC_EXEC_INVALID;
 	pad_args_t m;
-	if (!pad_args(cmd, inputs[0], outputs[0], &m)) return CCV_NNC_EXEC_INVALID;
+	if (!pad_args_fill(cmd, inputs[0], outputs[0], &m)) return CCV_NNC_EXEC_INVALID;
 	const size_t n = (size_t)m.bd[0] * m.bd[1] * m.bd[2] * m.bd[3];
 	if (n == 0) return CCV_NNC_EXEC_SUCCESS;
-	if (cmd.info.pad.type == PAD_ZERO) hipLaunchKernelGGL(HIP_KERNEL_NAME(pad_forw_kernel<PAD_ZERO>), dim3(grid_for(n, 256)), dim3(256), 0, stream_of(stream_context), (const float*)inputs[0]->data.f32, outputs[0]->data.f32, m, n);
-	else if (cmd.info.pad.type == PAD_REPLICATE) hipLaunchKernelGGL(HIP_KERNEL_NAME(pad_forw_kernel<PAD_REPLICATE>), dim3(grid_for(n, 256)), dim3(256), 0, stream_of(stream_context), (const float*)inputs[0]->data.f32, outputs[0]->data.f32, m, n);
+	if (cmd.info.pad.type == PAD_ZERO) hipLaunchKernelGGL(HIP_KERNEL_NAME(pad_forw_kernel<float, PAD_ZERO>), dim3(grid_for(n, 256)), dim3(256), 0, stream_of(stream_context), (const float*)inputs[0]->data.f32, outputs[0]->data.f32, m, n);
+	else if (cmd.info.pad.type == PAD_REPLICATE) hipLaunchKernelGGL(HIP_KERNEL_NAME(pad_forw_kernel<float, PAD_REPLICATE>), dim3(grid_for(n, 256)), dim3(256), 0, stream_of(stream_context), (const float*)inputs[0]->data.f32, outputs[0]->data.f32, m, n);
 	else return CCV_NNC_EXEC_INVALID;
 	HIP_ENFORCE(hipGetLastError());
 	return CCV_NNC_EXEC_SUCCESS;
 }
 static int _pad_back(EXEC_ARGS)
 { // g (padded shape) -> h (original shape): the crop (pad_cpu_ref.c:88-138)
+	int ret;
+	if (input_size >= 1 && output_size >= 1 && pad_half_route(cmd, flags, outputs[0], inputs[0], false, stream_context, &ret)) return ret;
 	if (input_size < 1 || output_size < 1 || !inputs[0] || !outputs[0] || CCV_GET_DATA_TYPE(inputs[0]->info.datatype) != CCV_32F) return CCV_NNC_EXEC_INVALID;
 	pad_args_t m;
-	if (!pad_args(cmd, outputs[0], inputs[0], &m)) return CCV_NNC_EXEC_INVALID;
+	if (!pad_args_fill(cmd, outputs[0], inputs[0], &m)) return CCV_NNC_EXEC_INVALID;
 	const size_t n = (size_t)m.ad[0] * m.ad[1] * m.ad[2] * m.ad[3];
 	if (n == 0) return CCV_NNC_EXEC_SUCCESS;
-	hipLaunchKernelGGL(pad_back_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream_of(stream_context), (const float*)inputs[0]->data.f32, outputs[0]->data.f32, m, n);
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(pad_back_kernel<float>), dim3(grid_for(n, 256)), dim3(256), 0, stream_of(stream_context), (const float*)inputs[0]->data.f32, outputs[0]->data.f32, m, n);
 	HIP_ENFORCE(hipGetLastError());
 	return CCV_NNC_EXEC_SUCCESS;
 }
 
 } // namespace
+
+namespace nnc {
+bool index_pad_half_applies(const ccv_nnc_cmd_t cmd, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
+{
+	if (input_size < 1 || output_size < 1 || !inputs[0] || !outputs[0]) return false;
+	index_plan_t ip;
+	pad_plan_t pp;
+	switch (cmd.cmd) {
+		case CCV_NNC_INDEX_SELECT_FORWARD: return input_size >= 2 && index_half_plan(true, flags, inputs[0], outputs[0], inputs[1], &ip);
+		case CCV_NNC_INDEX_SELECT_BACKWARD: return input_size >= 3 && index_half_plan(false, flags, outputs[0], inputs[0], inputs[2], &ip);
+		case CCV_NNC_PAD_FORWARD: return pad_half_plan(cmd, flags, inputs[0], outputs[0], true, &pp);
+		case CCV_NNC_PAD_BACKWARD: return pad_half_plan(cmd, flags, outputs[0], inputs[0], false, &pp);
+	}
+	return false;
+}
+} // namespace nnc
 
 #define NNC_REG(CMD, BACKEND, DATATYPES, EXEC) \
 	extern "C" void _register_command_##CMD##_backend_##BACKEND(ccv_nnc_cmd_backend_registry_t* const registry) \
