@@ -5,7 +5,7 @@
 //   NMS        lib/nnc/cmd/nms/ccv_nnc_nms_cpu_ref.c:29-225                    (nms/gpu/ccv_nnc_nms_gpu_ref.cu)
 //   ROI_ALIGN  lib/nnc/cmd/roi/ccv_nnc_roi_align_cpu_ref.c:18-324              (roi/gpu/ccv_nnc_roi_align_gpu_ref.cu:13-390)
 //   LSSC       lib/nnc/cmd/compression/ccv_nnc_lssc_cpu_ref.c:13-150           (compression/gpu/ccv_nnc_lssc_gpu_ref.cu)
-#include "common.h"
+#include "cmul_ops.h" // the CMUL modes, term and geometry; the half kernels and their plan
 #include <float.h>
 
 using namespace nnc;
@@ -23,22 +23,8 @@ static bool f32(const ccv_nnc_tensor_t* t) { return CCV_GET_DATA_TYPE(t->info.da
 //             without g: the conjugate of the other operand when nothing is broadcast, and -- as the reference's broadcasting
 //             branch does (cmul_cpu_ref.c:372-420) -- the PLAIN sum of the other operand when something is.
 // One thread per output pair; the reduced sub-space is walked in the reference's loop order (axis 0 outermost).
-struct shape4_t { int d[4]; long s[4]; };
-static bool shape4(const ccv_nnc_tensor_t* t, shape4_t* o)
-{
-	const int nd = tensor_nd(t->info.dim);
-	if (nd > 4 || nd < 1) return false;
-	int st[CCV_NNC_MAX_DIM_ALLOC];
-	tensor_strides(t, st);
-	for (int k = 0; k < 4; k++) {
-		const int j = k - (4 - nd);
-		o->d[k] = j >= 0 ? t->info.dim[j] : 1;
-		o->s[k] = (j >= 0 && o->d[k] != 1) ? st[j] : 0;
-	}
-	return true;
-}
-struct cmul_args_t { int od[4]; int rd[4]; long sx[4], sy[4], so[4]; }; // axis 3 counted in PAIRS, its strides in floats per pair
-enum { CM_MUL = 0, CM_MUL_CONJ = 1, CM_CONJ = 2, CM_SUM = 3 };
+// The modes, the per-term expression (cmul_term) and the geometry (cmul_geometry) are cmul_ops.h's, shared with the half kernels there: dense CCV_16F tensors run on
+// those as halves (tunable CMUL_HALF_NATIVE); everything else in half precision runs on fp32 images of its tensors through the kernel below.
 template <int MODE>
 __global__ void __launch_bounds__(256) cmul_kernel(const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ out, const cmul_args_t m, const size_t n)
 {
@@ -55,40 +41,24 @@ __global__ void __launch_bounds__(256) cmul_kernel(const float* __restrict__ x, 
 			const int i0 = o[0] + j0, i1 = o[1] + j1, i2 = o[2] + j2;
 			const long xo = i0 * m.sx[0] + i1 * m.sx[1] + i2 * m.sx[2] + o[3] * m.sx[3];
 			const float x0 = x[xo], x1 = x[xo + 1];
-			if (MODE == CM_CONJ) { re += x0; im += -x1; }
-			else if (MODE == CM_SUM) { re += x0; im += x1; }
+			if (MODE == CM_CONJ || MODE == CM_SUM) cmul_term<MODE>(re, im, x0, x1, 0.f, 0.f);
 			else {
 				const long yo = i0 * m.sy[0] + i1 * m.sy[1] + i2 * m.sy[2] + o[3] * m.sy[3];
 				const float y0 = y[yo], y1 = y[yo + 1];
-				if (MODE == CM_MUL) { re += x0 * y0 - x1 * y1; im += x0 * y1 + x1 * y0; }
-				else { re += x0 * y0 + x1 * y1; im += -x0 * y1 + x1 * y0; }
+				cmul_term<MODE>(re, im, x0, x1, y0, y1);
 			}
 		}
 		const long oo = o[0] * m.so[0] + o[1] * m.so[1] + o[2] * m.so[2] + o[3] * m.so[3];
 		out[oo] = re; out[oo + 1] = im;
 	}
 }
-// out = reduce over the axes out is 1 on (and x / y are not) of op(x, y); *broadcast = whether any axis was reduced or broadcast
+// out = reduce over the axes out is 1 on (and x / y are not) of op(x, y)
 template <int MODE>
 static int cmul_run(const ccv_nnc_tensor_t* x, const ccv_nnc_tensor_t* y, ccv_nnc_tensor_t* out, ccv_nnc_stream_context_t* ctx)
 {
-	shape4_t sx, sy, so;
 	if (!f32(x) || !f32(out) || (y && !f32(y))) return CCV_NNC_EXEC_INVALID;
-	if (!shape4(x, &sx) || !shape4(out, &so) || (y && !shape4(y, &sy))) return CCV_NNC_EXEC_INVALID;
 	cmul_args_t m;
-	for (int k = 0; k < 4; k++) {
-		int full = sx.d[k];
-		if (y && sy.d[k] > full) full = sy.d[k];
-		if (so.d[k] > full) full = so.d[k];
-		if ((sx.d[k] != full && sx.d[k] != 1) || (y && sy.d[k] != full && sy.d[k] != 1) || (so.d[k] != full && so.d[k] != 1)) return CCV_NNC_EXEC_INVALID;
-		m.od[k] = so.d[k];
-		m.rd[k] = so.d[k] == full ? 1 : full;
-		m.sx[k] = sx.s[k]; m.sy[k] = y ? sy.s[k] : 0; m.so[k] = so.s[k];
-	}
-	// the pair axis: even, dense, never broadcast (cmul_cpu_ref.c:94-95)
-	if ((so.d[3] & 1) || sx.d[3] != so.d[3] || (y && sy.d[3] != so.d[3]) || so.s[3] != 1 || sx.s[3] != 1 || (y && sy.s[3] != 1)) return CCV_NNC_EXEC_INVALID;
-	m.od[3] = so.d[3] / 2; m.rd[3] = 1;
-	m.sx[3] = 2; m.sy[3] = 2; m.so[3] = 2;
+	if (!cmul_geometry(x, y, out, &m, 0)) return CCV_NNC_EXEC_INVALID;
 	const size_t n = (size_t)m.od[0] * m.od[1] * m.od[2] * m.od[3];
 	if (n == 0) return CCV_NNC_EXEC_SUCCESS;
 	hipLaunchKernelGGL(HIP_KERNEL_NAME(cmul_kernel<MODE>), dim3(grid_for(n, 256)), dim3(256), 0, stream_of(ctx), (const float*)x->data.f32, y ? (const float*)y->data.f32 : 0, out->data.f32, m, n);
@@ -97,35 +67,71 @@ static int cmul_run(const ccv_nnc_tensor_t* x, const ccv_nnc_tensor_t* y, ccv_nn
 }
 static bool same_dims(const ccv_nnc_tensor_t* a, const ccv_nnc_tensor_t* b)
 {
-	shape4_t sa, sb;
-	if (!shape4(a, &sa) || !shape4(b, &sb)) return false;
+	cmul_shape4_t sa, sb;
+	if (!cmul_shape4(a, &sa) || !cmul_shape4(b, &sb)) return false;
 	for (int k = 0; k < 4; k++) if (sa.d[k] != sb.d[k]) return false;
 	return true;
 }
-static int _cmul_forw(EXEC_ARGS)
+// what a command launches, one operation per requested output: out = MODE(x, y)
+struct cmul_op_t { int mode; const ccv_nnc_tensor_t *x, *y; ccv_nnc_tensor_t* out; };
+static int cmul_forw_ops(ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, cmul_op_t ops[2])
 {
-	if (input_size < 2 || output_size < 1 || !inputs[0] || !inputs[1] || !outputs[0]) return CCV_NNC_EXEC_INVALID;
-	return cmul_run<CM_MUL>(inputs[0], inputs[1], outputs[0], stream_context);
+	if (input_size < 2 || output_size < 1 || !inputs[0] || !inputs[1] || !outputs[0]) return -1;
+	ops[0] = { CM_MUL, inputs[0], inputs[1], outputs[0] };
+	return 1;
 }
-static int _cmul_back(EXEC_ARGS)
+static int cmul_back_ops(ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, cmul_op_t ops[2])
 { // inputs (g, a, b), outputs (da, db)
-	if (input_size < 3 || output_size < 1) return CCV_NNC_EXEC_INVALID;
+	if (input_size < 3 || output_size < 1) return -1;
 	const ccv_nnc_tensor_t* g = inputs[0];
 	// "no broadcasting" as the reference decides it (cmul_cpu_ref.c:313-327): each requested output has its other operand's shape
 	bool plain = true;
 	for (int i = 0; i < 2 && i < output_size; i++)
-		if (outputs[i]) { if (!inputs[2 - i]) return CCV_NNC_EXEC_INVALID; plain = plain && same_dims(outputs[i], inputs[2 - i]); }
+		if (outputs[i]) { if (!inputs[2 - i]) return -1; plain = plain && same_dims(outputs[i], inputs[2 - i]); }
+	int n = 0;
 	for (int i = 0; i < 2 && i < output_size; i++) {
-		ccv_nnc_tensor_t* o = outputs[i];
-		if (!o) continue;
+		if (!outputs[i]) continue;
 		const ccv_nnc_tensor_t* other = inputs[2 - i]; // da needs b, db needs a
+		if (g) ops[n++] = { CM_MUL_CONJ, g, other, outputs[i] };
+		else ops[n++] = { plain ? CM_CONJ : CM_SUM, other, 0, outputs[i] };
+	}
+	return n;
+}
+// The half route (cmul_ops.h): every operation of the command passes cmul_half_plan, and where there are two the first writes nothing the second reads or writes.
+// n: what cmul_forw_ops / cmul_back_ops returned
+static bool cmul_half_command(const cmul_op_t* ops, const int n, const int flags, cmul_half_plan_t* plans)
+{
+	if (n < 1) return false;
+	for (int i = 0; i < n; i++)
+		if (!cmul_half_plan(ops[i].mode, ops[i].x, ops[i].y, ops[i].out, flags, &plans[i])) return false;
+	if (n == 2 && plans[0].nv && (cmul_overlap(ops[0].out, ops[1].x) || (ops[1].y && cmul_overlap(ops[0].out, ops[1].y)) || cmul_overlap(ops[0].out, ops[1].out))) return false;
+	return true;
+}
+static int cmul_exec(const char* row, const cmul_op_t* ops, const int n, const int flags, ccv_nnc_stream_context_t* ctx)
+{
+	if (n < 0) return CCV_NNC_EXEC_INVALID;
+	cmul_half_plan_t plans[2];
+	const bool half = cmul_half_command(ops, n, flags, plans);
+	for (int i = 0; i < n; i++) {
 		int ret;
-		if (g) ret = cmul_run<CM_MUL_CONJ>(g, other, o, stream_context);
-		else if (plain) ret = cmul_run<CM_CONJ>(other, 0, o, stream_context);
-		else ret = cmul_run<CM_SUM>(other, 0, o, stream_context);
+		if (half) ret = cmul_half_run(row, plans[i], ctx);
+		else if (ops[i].mode == CM_MUL) ret = cmul_run<CM_MUL>(ops[i].x, ops[i].y, ops[i].out, ctx);
+		else if (ops[i].mode == CM_MUL_CONJ) ret = cmul_run<CM_MUL_CONJ>(ops[i].x, ops[i].y, ops[i].out, ctx);
+		else if (ops[i].mode == CM_CONJ) ret = cmul_run<CM_CONJ>(ops[i].x, 0, ops[i].out, ctx);
+		else ret = cmul_run<CM_SUM>(ops[i].x, 0, ops[i].out, ctx);
 		if (ret != CCV_NNC_EXEC_SUCCESS) return ret;
 	}
 	return CCV_NNC_EXEC_SUCCESS;
+}
+static int _cmul_forw(EXEC_ARGS)
+{
+	cmul_op_t ops[2];
+	return cmul_exec("cmul_forw", ops, cmul_forw_ops(inputs, input_size, outputs, output_size, ops), flags, stream_context);
+}
+static int _cmul_back(EXEC_ARGS)
+{
+	cmul_op_t ops[2];
+	return cmul_exec("cmul_back", ops, cmul_back_ops(inputs, input_size, outputs, output_size, ops), flags, stream_context);
 }
 
 // =====================================================================================================================
@@ -465,6 +471,17 @@ static int _lssc_back(EXEC_ARGS)
 }
 
 } // namespace
+
+namespace nnc {
+bool cmul_half_applies(const ccv_nnc_cmd_t cmd, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
+{
+	cmul_op_t ops[2];
+	cmul_half_plan_t plans[2];
+	if (cmd.cmd == CCV_NNC_CMUL_FORWARD) return cmul_half_command(ops, cmul_forw_ops(inputs, input_size, outputs, output_size, ops), flags, plans);
+	if (cmd.cmd == CCV_NNC_CMUL_BACKWARD) return cmul_half_command(ops, cmul_back_ops(inputs, input_size, outputs, output_size, ops), flags, plans);
+	return false;
+}
+} // namespace nnc
 
 #define ALL_FORMATS (CCV_TENSOR_FORMAT_NCHW | CCV_TENSOR_FORMAT_NHWC | CCV_TENSOR_FORMAT_CHWN)
 #define NNC_REG(CMD, BACKEND, FORMATS, DATATYPES, EXEC) \

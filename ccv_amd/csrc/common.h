@@ -281,6 +281,7 @@ enum {
 	TUNE_UPSAMPLE_HALF_NATIVE, // UPSAMPLE_FORWARD / UPSAMPLE_BACKWARD (nearest and bilinear, align_corners or not) read and write dense CCV_16F tensors in the NCHW and NHWC layouts as halves themselves on the kernels of upsample_ops.h (1), or run on fp32 images of them (0); 2 = as 1 on the scalar instances everywhere (measurements)
 	TUNE_INDEX_PAD_HALF_NATIVE, // INDEX_SELECT_FORWARD / INDEX_SELECT_BACKWARD and PAD_FORWARD / PAD_BACKWARD read and write dense CCV_16F tensors as halves themselves on the kernels of index_ops.h (1), or run on fp32 images of them (0)
 	TUNE_INDEX_BACK_TILES,  // INDEX_SELECT_BACKWARD on dense tensors, fp32 and half: a wave per tile of destination rows and columns sums its sources in row order in LDS and writes the tile once, zeros included (1), or zero_rows_kernel and index_scatter_add_kernel, one thread per column (0; a half command then keeps its fp32 images).  The sums are bit for bit the same
+	TUNE_CMUL_HALF_NATIVE,  // CMUL_FORWARD / CMUL_BACKWARD (rotary position embeddings) read and write dense CCV_16F tensors as halves themselves on the kernels of cmul_ops.h (1), or run on fp32 images of them (0)
 	TUNE_COUNT
 };
 static_assert(TUNE_GRID_WG_PER_CU == 3, "grid_for() above names this key by value");
@@ -349,6 +350,9 @@ bool upsample_half_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t*
 // cmd_index_pad.cpp: is this INDEX_SELECT / PAD command (forward or backward) one the half kernels of index_ops.h take -- tuning keys, no accumulation, table and selection
 // (pad: both tensors) dense CCV_16F ones, fewer than 2^31 elements (index_half_plan / pad_half_plan)?  The exec functions decide with the same plans.
 bool index_pad_half_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size);
+// cmd_detect.cpp: is this CMUL_FORWARD / CMUL_BACKWARD command one the half kernels of cmul_ops.h take -- tuning key, no accumulation, every used tensor a dense CCV_16F
+// one, shapes cmul_geometry takes, fewer than 2^31 elements, no unsafe overlap, for EVERY requested output (cmul_half_plan)?  The exec functions decide with the same plan.
+bool cmul_half_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size);
 bool softmax_half_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size);
 bool any_half_tensor(ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size);
 int half_to_float(const void* in, float* out, size_t n, ccv_nnc_stream_context_t* ctx);

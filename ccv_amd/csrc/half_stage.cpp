@@ -145,7 +145,7 @@ void warn_refused(const uint32_t cmd, const int ret)
 }
 
 // Rows whose kernels read and write their LARGE tensors in half precision themselves (loads / stores of halves, fp32 arithmetic:
-// cmd_ew.cpp, cmd_norm.cpp, cmd_pool.cpp, cmd_act_opt.cpp, cmd_bcast.cpp's plane-scale MUL, row_ops.h, group_ops.h, bcast_ops.h, upsample_ops.h, index_ops.h).  Bit i of `in` / `out` = that input / output stays in its own memory when every tensor
+// cmd_ew.cpp, cmd_norm.cpp, cmd_pool.cpp, cmd_act_opt.cpp, cmd_bcast.cpp's plane-scale MUL, row_ops.h, group_ops.h, bcast_ops.h, upsample_ops.h, index_ops.h, cmul_ops.h).  Bit i of `in` / `out` = that input / output stays in its own memory when every tensor
 // named by the masks is a dense CCV_16F tensor; the row's small tensors (batch-norm statistics, ...) still get fp32 images.
 static long g_half_staged = 0, g_half_native = 0; // nnc_mi355x_debug_half_counts (test hook; not synchronised: counts, not control)
 // NNC_MI355X_HALF_STATS=1: one line per command at unload -- which rows of a run went through fp32 images of their half tensors (and how many tensors)
@@ -263,6 +263,9 @@ static const native_half_t g_native_half[] = {
 	{ CCV_NNC_INDEX_SELECT_BACKWARD, 1u << 0, 1u << 0, index_pad_half_applies },                                               // g, _, (indices) -> h
 	{ CCV_NNC_PAD_FORWARD, 1u << 0, 1u << 0, index_pad_half_applies },                                                         // a -> b
 	{ CCV_NNC_PAD_BACKWARD, 1u << 0, 1u << 0, index_pad_half_applies },                                                        // g -> h
+	// cmul_ops.h: the complex multiply (rotary embeddings), where cmul_half_plan takes every requested output
+	{ CCV_NNC_CMUL_FORWARD, (1u << 0) | (1u << 1), 1u << 0, cmul_half_applies },                                               // a, b -> c
+	{ CCV_NNC_CMUL_BACKWARD, (1u << 0) | (1u << 1) | (1u << 2), (1u << 0) | (1u << 1), cmul_half_applies },                    // g, a, b -> da, db
 };
 static const native_half_t* native_half_row(const ccv_nnc_cmd_t command, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
 {
