@@ -15,9 +15,11 @@
 //                        through here: they use the two-stage column reducers of cmd_ew.cpp / cmd_norm.cpp.)
 // One pattern of MUL leaves them: an activation tensor times one value per (image, channel), the squeeze-excite scale -- mul_planes.h, mul_planes_plan below.
 // Dense CCV_16F commands of ADD, same-shape MUL, REDUCE_SUM and REDUCE_MEAN whose shapes are flat, a period or runs leave them too: bcast_ops.h (BCAST_HALF_ROUTE).
+// So do a trainer's passes over its half gradients -- REDUCE_NORM2 and REDUCE_ISNAN of a whole dense CCV_16F tensor, MUL of one by a one-element tensor: grad_ops.h (GRAD_HALF_ROUTE).
 #include "common.h"
 #include "mul_planes.h"
 #include "bcast_ops.h"
+#include "grad_ops.h"
 #include <math.h>
 
 using namespace nnc;
@@ -328,6 +330,7 @@ static int _mul_forw(EXEC_ARGS)
 	mul_plan_t mp;
 	if (mul_planes_plan(cmd, flags, inputs, input_size, outputs, output_size, &mp)) return mp.dt == CCV_16F ? mul_planes_run<half_t>(mp, cmd.info.blas.a[0], stream_context) : mul_planes_run<float>(mp, cmd.info.blas.a[0], stream_context);
 	BCAST_HALF_ROUTE;
+	GRAD_HALF_ROUTE; // a dense half tensor by a one-element tensor: grad_ops.h
 	if (input_size < 1 || output_size < 1 || !inputs[0] || !outputs[0] || !f32(inputs[0])) return CCV_NNC_EXEC_INVALID;
 	const ccv_nnc_tensor_t* b = input_size > 1 ? inputs[1] : 0;
 	if (!b) { FScale f; f.p = cmd.info.blas.a[0]; return bcast_map(f, inputs[0], 0, outputs[0], stream_context); }
@@ -503,6 +506,7 @@ static int _reduce_min_forw(EXEC_ARGS)
 }
 static int _reduce_norm2_forw(EXEC_ARGS)
 {
+	GRAD_HALF_ROUTE; // a whole dense half tensor: grad_ops.h
 	if (input_size < 1 || output_size < 1 || !inputs[0] || !outputs[0] || !f32(inputs[0])) return CCV_NNC_EXEC_INVALID;
 	return bcast_reduce<FSquare, RED_NORM2>(FSquare(), inputs[0], 0, outputs[0], stream_context);
 }
@@ -654,6 +658,7 @@ static int _masked_fill_back(EXEC_ARGS)
 struct FIsNan { __device__ float operator()(float x, float) const { return __int_as_float(x != x ? 1 : 0); } };
 static int _reduce_isnan_forw(EXEC_ARGS)
 {
+	GRAD_HALF_ROUTE; // a whole dense half tensor: grad_ops.h
 	if (input_size < 1 || output_size < 1 || !inputs[0] || !outputs[0]) return CCV_NNC_EXEC_INVALID;
 	if (CCV_GET_DATA_TYPE(inputs[0]->info.datatype) != CCV_32F || CCV_GET_DATA_TYPE(outputs[0]->info.datatype) != CCV_32S) return CCV_NNC_EXEC_INVALID;
 	return bcast_reduce<FIsNan, RED_MAX>(FIsNan(), inputs[0], 0, outputs[0], stream_context);
@@ -681,6 +686,17 @@ int bcast_half_exec(const ccv_nnc_cmd_t cmd, const int flags, ccv_nnc_tensor_t* 
 	bcast_plan_t bp;
 	if (!bcast_half_plan(cmd, flags, inputs, input_size, outputs, output_size, &bp)) return BCAST_HALF_NOT_TAKEN;
 	return bcast_half_run(bp, ctx);
+}
+bool grad_half_applies(const ccv_nnc_cmd_t cmd, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
+{
+	grad_plan_t gp;
+	return grad_half_plan(cmd, flags, inputs, input_size, outputs, output_size, &gp);
+}
+int grad_half_exec(const ccv_nnc_cmd_t cmd, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const ctx)
+{
+	grad_plan_t gp;
+	if (!grad_half_plan(cmd, flags, inputs, input_size, outputs, output_size, &gp)) return GRAD_HALF_NOT_TAKEN;
+	return grad_half_run(gp, ctx);
 }
 bool mul_planes_applies(const ccv_nnc_cmd_t cmd, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
 {

@@ -282,6 +282,7 @@ enum {
 	TUNE_INDEX_PAD_HALF_NATIVE, // INDEX_SELECT_FORWARD / INDEX_SELECT_BACKWARD and PAD_FORWARD / PAD_BACKWARD read and write dense CCV_16F tensors as halves themselves on the kernels of index_ops.h (1), or run on fp32 images of them (0)
 	TUNE_INDEX_BACK_TILES,  // INDEX_SELECT_BACKWARD on dense tensors, fp32 and half: a wave per tile of destination rows and columns sums its sources in row order in LDS and writes the tile once, zeros included (1), or zero_rows_kernel and index_scatter_add_kernel, one thread per column (0; a half command then keeps its fp32 images).  The sums are bit for bit the same
 	TUNE_CMUL_HALF_NATIVE,  // CMUL_FORWARD / CMUL_BACKWARD (rotary position embeddings) read and write dense CCV_16F tensors as halves themselves on the kernels of cmul_ops.h (1), or run on fp32 images of them (0)
+	TUNE_GRAD_HALF_NATIVE,  // whole-tensor REDUCE_NORM2_FORWARD and REDUCE_ISNAN_FORWARD of a dense CCV_16F tensor and MUL_FORWARD of one by a one-element tensor (gradient clipping and the NaN check of a half-precision trainer) read and write the halves themselves on the kernels of grad_ops.h (1), or run on fp32 images of them (0)
 	TUNE_COUNT
 };
 static_assert(TUNE_GRID_WG_PER_CU == 3, "grid_for() above names this key by value");
@@ -353,6 +354,12 @@ bool index_pad_half_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t
 // cmd_detect.cpp: is this CMUL_FORWARD / CMUL_BACKWARD command one the half kernels of cmul_ops.h take -- tuning key, no accumulation, every used tensor a dense CCV_16F
 // one, shapes cmul_geometry takes, fewer than 2^31 elements, no unsafe overlap, for EVERY requested output (cmul_half_plan)?  The exec functions decide with the same plan.
 bool cmul_half_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size);
+// cmd_bcast.cpp: is this REDUCE_NORM2_FORWARD / REDUCE_ISNAN_FORWARD / MUL_FORWARD command one the half kernels of grad_ops.h take -- tuning key, no accumulation, a dense
+// CCV_16F tensor of fewer than 2^31 elements reduced to one element, or multiplied by a one-element tensor (grad_half_plan)?  The exec functions decide with the same plan.
+bool grad_half_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size);
+constexpr int GRAD_HALF_NOT_TAKEN = 1; // grad_half_exec: the command is not one of grad_ops.h's, nothing was launched (else what the native kernels returned, CCV_NNC_EXEC_*)
+int grad_half_exec(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size, ccv_nnc_stream_context_t* ctx);
+#define GRAD_HALF_ROUTE do { const int taken = nnc::grad_half_exec(cmd, flags, inputs, input_size, outputs, output_size, stream_context); if (taken != nnc::GRAD_HALF_NOT_TAKEN) return taken; } while (0)
 bool softmax_half_applies(const ccv_nnc_cmd_t cmd, int flags, ccv_nnc_tensor_t* const* inputs, int input_size, ccv_nnc_tensor_t* const* outputs, int output_size);
 bool any_half_tensor(ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size);
 int half_to_float(const void* in, float* out, size_t n, ccv_nnc_stream_context_t* ctx);

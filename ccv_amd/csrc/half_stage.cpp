@@ -145,7 +145,7 @@ void warn_refused(const uint32_t cmd, const int ret)
 }
 
 // Rows whose kernels read and write their LARGE tensors in half precision themselves (loads / stores of halves, fp32 arithmetic:
-// cmd_ew.cpp, cmd_norm.cpp, cmd_pool.cpp, cmd_act_opt.cpp, cmd_bcast.cpp's plane-scale MUL, row_ops.h, group_ops.h, bcast_ops.h, upsample_ops.h, index_ops.h, cmul_ops.h).  Bit i of `in` / `out` = that input / output stays in its own memory when every tensor
+// cmd_ew.cpp, cmd_norm.cpp, cmd_pool.cpp, cmd_act_opt.cpp, cmd_bcast.cpp's plane-scale MUL, row_ops.h, group_ops.h, bcast_ops.h, upsample_ops.h, index_ops.h, cmul_ops.h, grad_ops.h).  Bit i of `in` / `out` = that input / output stays in its own memory when every tensor
 // named by the masks is a dense CCV_16F tensor; the row's small tensors (batch-norm statistics, ...) still get fp32 images.
 static long g_half_staged = 0, g_half_native = 0; // nnc_mi355x_debug_half_counts (test hook; not synchronised: counts, not control)
 // NNC_MI355X_HALF_STATS=1: one line per command at unload -- which rows of a run went through fp32 images of their half tensors (and how many tensors)
@@ -218,6 +218,11 @@ static const native_half_t g_native_half[] = {
 	// bcast_ops.h: ADD, same-shape MUL (behind the plane-scale rows), REDUCE_SUM / REDUCE_MEAN and SCALAR_MUL where bcast_half_plan takes the shapes (flat, a period, runs)
 	{ CCV_NNC_MUL_FORWARD, (1u << 0) | (1u << 1), 1u << 0, bcast_half_applies },
 	{ CCV_NNC_MUL_BACKWARD, (1u << 0) | (1u << 1) | (1u << 2), (1u << 0) | (1u << 1), bcast_half_applies },
+	// grad_ops.h (behind the MUL rows above: whatever those take they still take): a dense half tensor by a one-element tensor -- both operands half; the large
+	// one first, then second, with a CCV_32F scalar, which is no half and passes as itself
+	{ CCV_NNC_MUL_FORWARD, (1u << 0) | (1u << 1), 1u << 0, grad_half_applies },
+	{ CCV_NNC_MUL_FORWARD, 1u << 0, 1u << 0, grad_half_applies },
+	{ CCV_NNC_MUL_FORWARD, 1u << 1, 1u << 0, grad_half_applies },
 	{ CCV_NNC_ADD_FORWARD, (1u << 0) | (1u << 1), 1u << 0, bcast_half_applies },             // a, b -> c
 	{ CCV_NNC_ADD_BACKWARD, 1u << 0, (1u << 0) | (1u << 1), bcast_half_applies },            // g -> da, db
 	{ CCV_NNC_REDUCE_SUM_FORWARD, 1u << 0, 1u << 0, bcast_half_applies },                    // a -> b
@@ -266,6 +271,11 @@ static const native_half_t g_native_half[] = {
 	// cmul_ops.h: the complex multiply (rotary embeddings), where cmul_half_plan takes every requested output
 	{ CCV_NNC_CMUL_FORWARD, (1u << 0) | (1u << 1), 1u << 0, cmul_half_applies },                                               // a, b -> c
 	{ CCV_NNC_CMUL_BACKWARD, (1u << 0) | (1u << 1) | (1u << 2), (1u << 0) | (1u << 1), cmul_half_applies },                    // g, a, b -> da, db
+	// grad_ops.h: a whole dense half tensor reduced to one element, where grad_half_plan takes the command.  A half result is named first: the row without it
+	// would stage it.  CCV_32F / CCV_32S results are no halves and pass as themselves
+	{ CCV_NNC_REDUCE_NORM2_FORWARD, 1u << 0, 1u << 0, grad_half_applies },                                                     // a -> b, both half
+	{ CCV_NNC_REDUCE_NORM2_FORWARD, 1u << 0, 0, grad_half_applies },                                                           // a -> b (fp32)
+	{ CCV_NNC_REDUCE_ISNAN_FORWARD, 1u << 0, 0, grad_half_applies },                                                           // a -> b (int32)
 };
 static const native_half_t* native_half_row(const ccv_nnc_cmd_t command, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size)
 {

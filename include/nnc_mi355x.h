@@ -495,7 +495,10 @@ long nnc_mi355x_debug_exec_count(void);
  * INDEX_SELECT_FORWARD / BACKWARD and PAD_FORWARD / BACKWARD on CCV_16F tensors back on fp32 images; NNC_MI355X_INDEX_BACK_TILES=0 / nnc_mi355x_tune_set("INDEX_BACK_TILES", 0)
  * puts INDEX_SELECT_BACKWARD, fp32 and half, back on index_scatter_add_kernel behind a zeroing pass (a half command then runs on fp32 images).  The bits are the same.
  * Likewise the half complex multiply (cmul_ops.h; rotary position embeddings): NNC_MI355X_CMUL_HALF_NATIVE=0 / nnc_mi355x_tune_set("CMUL_HALF_NATIVE", 0) puts CMUL_FORWARD /
- * BACKWARD on CCV_16F tensors back on fp32 images, with the same bits. */
+ * BACKWARD on CCV_16F tensors back on fp32 images, with the same bits.
+ * Likewise a trainer's passes over half gradients (grad_ops.h; gradient clipping and the NaN check): NNC_MI355X_GRAD_HALF_NATIVE=0 / nnc_mi355x_tune_set("GRAD_HALF_NATIVE", 0)
+ * puts whole-tensor REDUCE_NORM2_FORWARD / REDUCE_ISNAN_FORWARD of a dense CCV_16F tensor and MUL_FORWARD of one by a one-element tensor back on fp32 images.  The NaN
+ * flag and the product carry the same bits; the norm's fp32 sum has another (fixed) order and may differ in its last bits. */
 void nnc_mi355x_debug_half_counts(long* staged, long* native);
 /* Performance tunables (policy only -- results do not depend on them beyond floating-point re-association): by name, e.g.
  * "WINO_SLICE_KB"; the environment variable NNC_MI355X_<NAME> sets the same value at first use.  Returns 0 / -1 (unknown). */
