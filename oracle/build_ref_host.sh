@@ -62,9 +62,12 @@ wait
 ls $OUT/int | tr '\n' ' '; echo
 # 4. the reference's CPU unit tests (test/unit/nnc/*.tests.c) against the SAME host + backend libraries: linking the GPU
 #    backend in must leave every CPU-tensor code path of the host (graphs, autograd, cnnp, CPU backends) as it was.
-#    They run from $OUT/unit/run/test/unit/nnc, a scratch mirror whose data/ and samples/ point back into $REF.
+#    They run from $OUT/unit/run/test/unit/nnc, a scratch mirror whose data/ files and samples/ point back into $REF.
+#    data/ itself is a directory of the mirror: tensor.tests.c writes data/tensor.bin, and $REF is not ours to write to.
 mkdir -p $OUT/unit/run/test/unit/nnc/gen
-ln -sfn $REF/test/unit/nnc/data $OUT/unit/run/test/unit/nnc/data
+[ -L $OUT/unit/run/test/unit/nnc/data ] && rm $OUT/unit/run/test/unit/nnc/data  # (a mirror from before: one link to the whole directory)
+mkdir -p $OUT/unit/run/test/unit/nnc/data
+ln -sf $REF/test/unit/nnc/data/* $OUT/unit/run/test/unit/nnc/data/
 ln -sfn $REF/samples $OUT/unit/run/samples
 UNIT_SKIP=${UNIT_SKIP:-"cblas"}
 for src in $REF/test/unit/nnc/*.tests.c; do

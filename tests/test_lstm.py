@@ -182,11 +182,9 @@ def _run_inner(lib, case, dtype, tol, persistent):
 def test_lstm_forward_backward(backend, case, persistent):
     """The three forms of the sweep (tuning keys LSTM_PERSISTENT, LSTM_ROWS): the whole sequence of a pseudo-layer in one launch with a workgroup per two batch rows
     and all of R in its registers (hidden size <= 128, nothing passes between workgroups); in one launch with the hidden units split over workgroups that hand the state
-    to each other through tagged words; and a launch per step.  The backward command reads the reserved space any of them wrote."""
-    if persistent >= 2 and case[3] > 128:
-        pytest.skip("hidden size > 128: the default is the split form (the next parameter)")
-    if persistent and case[4] and case[4] != case[3]:
-        pytest.skip("a projection always takes the per-step form")
+    to each other through tagged words; and a launch per step.  The backward command reads the reserved space any of them wrote.
+    Every case runs under every key: where a form does not apply (hidden size > 128 under the rows keys: the split form; a projection: always
+    per step) the command must take the form that does, which _run checks by the kernel's name, and give the same numbers."""
     _run(backend, case, persistent=persistent)
 
 
