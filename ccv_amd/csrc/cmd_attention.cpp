@@ -239,8 +239,8 @@ __global__ void __launch_bounds__(256) sdpa_forw_mfma_kernel(const sdpa_geom_t g
 //   O^T [Dv x 32 rows] += V^T P^T        two sub-steps of 16 keys; the lane holds the probabilities of the keys ky(r) = (r & 3) + 8 (r >> 2) + 4 half of its row, so
 //                                        sub-step t takes registers 8 t .. 8 t + 7 -- rounded to half, still in place -- as B, and A = the same eight keys of column
 //                                        dv = l & 31 out of a TRANSPOSED V tile in LDS ([dv][key]: two 8-byte reads: keys 16 t + 4 half + 0..3 and + 8)
-// Conditions: D % 16 == 0, Dv % 32 == 0, both <= 128, 16-byte aligned rows; an additive mask is a CCV_16F tensor too (other shapes, and the head projection, go through
-// fp32 images and the fp32 kernels).  The log-sum-exp output, if asked for, is fp32.
+// Conditions: D % 16 == 0, Dv % 32 == 0, both <= 128, 16-byte aligned rows; an additive mask is a CCV_16F tensor too (other head sizes in 8s up to 256:
+// sdpa_anyd_f16.h below; everything else goes through fp32 images and the fp32 kernels).  The log-sum-exp output, if asked for, is fp32.
 template <int DS, int TV> // DS = D / 16 (1 .. 8), TV = Dv / 32 (1 .. 4)
 __global__ void __launch_bounds__(256) sdpa_forw_f16_kernel(const sdpa_geom_t g, const half_t* __restrict__ q, const half_t* __restrict__ k, const half_t* __restrict__ v, const half_t* __restrict__ mask, half_t* __restrict__ o, float* __restrict__ lse)
 {
@@ -335,6 +335,9 @@ __global__ void __launch_bounds__(256) sdpa_forw_f16_kernel(const sdpa_geom_t g,
 		if (lse && lh == 0) lse[((long)b * g.Hq + h) * g.R + x] = l_run > 0.f ? m_run + logf(l_run) : -INFINITY;
 	}
 }
+
+// ---- forward in half precision for every head size in 8s up to 256: sdpa_fwd_anyd_f16_kernel and its launcher ------------------------------------------------
+#include "sdpa_anyd_f16.h"
 
 // delta[b][h][x] = sum_d g[b, x, h, d] * o[b, x, h, d]   (o: the scratch copy, dense [B][R][Hq][Dv])
 __global__ void __launch_bounds__(256) sdpa_delta_kernel(const sdpa_geom_t g, const float* __restrict__ gr, const long g_sb, const long g_sr, const long g_sh, const float* __restrict__ o, float* __restrict__ delta)
@@ -968,6 +971,8 @@ static int sdpa_forward_launch(const sdpa_geom_t& g, const float* q, const float
 	return CCV_NNC_EXEC_SUCCESS;
 }
 
+static bool sdpa_projection_ok(const sdpa_geom_t& g, const ccv_nnc_tensor_t* c, const ccv_nnc_tensor_t* d, const ccv_nnc_tensor_t* w, const ccv_nnc_tensor_t* bias);
+static int sdpa_projection(const sdpa_geom_t& g, ccv_nnc_tensor_t* c, ccv_nnc_tensor_t* d, const ccv_nnc_tensor_t* w, const ccv_nnc_tensor_t* bias, ccv_nnc_stream_context_t* stream_context);
 static int _sdpa_forw(EXEC_ARGS)
 { // inputs (q, k, v, [mask], [w], [bias]); outputs (o, [lse], [the attention output before the projection])
 	if (input_size < 3 || output_size < 1 || !inputs[0] || !inputs[1] || !inputs[2]) return CCV_NNC_EXEC_INVALID;
@@ -990,11 +995,21 @@ static int _sdpa_forw(EXEC_ARGS)
 	}
 	int ret = sdpa_forward_launch(g, inputs[0]->data.f32, inputs[1]->data.f32, inputs[2]->data.f32, mask ? mask->data.f32 : 0, c->data.f32, lse, stream_of(stream_context));
 	if (ret != CCV_NNC_EXEC_SUCCESS || !w) return ret;
-	// unify heads: d[B * R, E] = c[B * R, E] w[E, E]^T (+ bias), E = Hq * Dv  (cpu_ref.c:185-252)
-	ccv_nnc_tensor_t* const d = outputs[0];
+	if (!sdpa_projection_ok(g, c, outputs[0], w, bias)) return CCV_NNC_EXEC_INVALID;
+	return sdpa_projection(g, c, outputs[0], w, bias, stream_context);
+}
+
+// unify heads: d[B * R, E] = c[B * R, E] w[E, E]^T (+ bias), E = Hq * Dv  (cpu_ref.c:185-252): a GEMM_FORWARD on the tensors as they are -- fp32, or all CCV_16F
+// (the f16 contraction core)
+static bool sdpa_projection_ok(const sdpa_geom_t& g, const ccv_nnc_tensor_t* const c, const ccv_nnc_tensor_t* const d, const ccv_nnc_tensor_t* const w, const ccv_nnc_tensor_t* const bias)
+{
 	const int E = g.Hq * g.Dv;
-	if (!d || !tensor_contiguous(c) || !tensor_contiguous(d) || !tensor_contiguous(w) || tensor_nd(w->info.dim) != 2 || w->info.dim[0] != E || w->info.dim[1] != E) return CCV_NNC_EXEC_INVALID;
-	if (tensor_count(d->info) != (size_t)g.B * g.R * E || (bias && tensor_count(bias->info) != (size_t)E)) return CCV_NNC_EXEC_INVALID;
+	if (!d || !tensor_contiguous(c) || !tensor_contiguous(d) || !tensor_contiguous(w) || tensor_nd(w->info.dim) != 2 || w->info.dim[0] != E || w->info.dim[1] != E) return false;
+	return tensor_count(d->info) == (size_t)g.B * g.R * E && (!bias || tensor_count(bias->info) == (size_t)E);
+}
+static int sdpa_projection(const sdpa_geom_t& g, ccv_nnc_tensor_t* const c, ccv_nnc_tensor_t* const d, const ccv_nnc_tensor_t* const w, const ccv_nnc_tensor_t* const bias, ccv_nnc_stream_context_t* const stream_context)
+{
+	const int E = g.Hq * g.Dv;
 	ccv_nnc_tensor_t a2 = *c, d2 = *d;
 	memset(a2.info.dim, 0, sizeof(a2.info.dim)); memset(d2.info.dim, 0, sizeof(d2.info.dim));
 	a2.info.dim[0] = g.B * g.R; a2.info.dim[1] = E; d2.info.dim[0] = g.B * g.R; d2.info.dim[1] = E;
@@ -1028,16 +1043,24 @@ static void sdpa_forw_f16_launch(const sdpa_geom_t& g, const half_t* const qp, c
 #undef SDPA_F16_TV
 	HIP_ENFORCE(hipGetLastError());
 }
-// CCV_16F tensors: the f16 kernel where its conditions hold (CCV_NNC_EXEC_NO_KERNEL = not this path: the caller goes through fp32 images)
+// CCV_16F tensors: sdpa_forw_f16_kernel where its conditions hold, sdpa_fwd_anyd_f16_kernel for the other head sizes in 8s up to 256, the head projection as a half
+// GEMM_FORWARD behind either (CCV_NNC_EXEC_NO_KERNEL = not this path: the caller goes through fp32 images)
 static int sdpa_forw_half(EXEC_ARGS)
 {
 	if (input_size < 3 || output_size < 1 || !inputs[0] || !inputs[1] || !inputs[2] || !outputs[0]) return CCV_NNC_EXEC_NO_KERNEL;
-	for (int i = 4; i < input_size; i++) if (inputs[i]) return CCV_NNC_EXEC_NO_KERNEL; // the head projection: the fp32 route
-	for (int i = 2; i < output_size; i++) if (outputs[i]) return CCV_NNC_EXEC_NO_KERNEL;
+	const long anyd = tune(TUNE_SDPA_F16_ANYD);
+	// the head projection: w, bias and both outputs CCV_16F too (mixed types, and every projection with the key at 0: the fp32 route)
+	const ccv_nnc_tensor_t* const w = input_size > 4 ? inputs[4] : 0;
+	const ccv_nnc_tensor_t* const bias = input_size > 5 ? inputs[5] : 0;
+	for (int i = 6; i < input_size; i++) if (inputs[i]) return CCV_NNC_EXEC_NO_KERNEL;
+	for (int i = 3; i < output_size; i++) if (outputs[i]) return CCV_NNC_EXEC_NO_KERNEL;
+	if (w) {
+		if (!anyd || output_size < 3 || !outputs[2] || CCV_GET_DATA_TYPE(w->info.datatype) != CCV_16F || (bias && CCV_GET_DATA_TYPE(bias->info.datatype) != CCV_16F) || CCV_GET_DATA_TYPE(outputs[0]->info.datatype) != CCV_16F) return CCV_NNC_EXEC_NO_KERNEL;
+	} else if (bias || (output_size > 2 && outputs[2])) return CCV_NNC_EXEC_NO_KERNEL;
 	const ccv_nnc_tensor_t* const mask = input_size > 3 ? inputs[3] : 0;
 	if (!tune(TUNE_SDPA_MFMA)) return CCV_NNC_EXEC_NO_KERNEL;
 	const ccv_nnc_tensor_t* const q = inputs[0]; const ccv_nnc_tensor_t* const k = inputs[1]; const ccv_nnc_tensor_t* const v = inputs[2];
-	ccv_nnc_tensor_t* const c = outputs[0];
+	ccv_nnc_tensor_t* const c = w ? outputs[2] : outputs[0];
 	ccv_nnc_tensor_t* const lse_t = output_size > 1 ? outputs[1] : 0;
 	bhd_t qi, ki, vi, ci;
 	if (!bhd(q, &qi, CCV_16F) || !bhd(k, &ki, CCV_16F) || !bhd(v, &vi, CCV_16F) || !bhd(c, &ci, CCV_16F)) return CCV_NNC_EXEC_NO_KERNEL;
@@ -1052,7 +1075,13 @@ static int sdpa_forw_half(EXEC_ARGS)
 	if (ci.b != g.B || ci.n != g.R || ci.h != g.Hq || ci.d != g.Dv) return CCV_NNC_EXEC_INVALID;
 	g.o_sb = ci.sb; g.o_sr = ci.sn; g.o_sh = ci.sh;
 	if (mask && !sdpa_mask_geometry(mask, &g, CCV_16F)) return CCV_NNC_EXEC_NO_KERNEL;
-	if (g.D % 16 || g.Dv % 32 || g.D > 128 || g.Dv > 128 || g.D < 16) return CCV_NNC_EXEC_NO_KERNEL;
+	// sdpa_forw_f16_kernel keeps the shapes it takes; sdpa_fwd_anyd_f16_kernel (sdpa_anyd_f16.h) takes the others in 8s up to 256 (key SDPA_F16_ANYD: 0 = never,
+	// 2 = every shape it can, for measurements)
+	const bool old_ok = !(g.D % 16 || g.Dv % 32 || g.D > 128 || g.Dv > 128 || g.D < 16);
+	const bool anyd_ok = anyd && !(g.D % 8 || g.Dv % 8 || g.D > 256 || g.Dv > 256 || g.D < 8 || g.Dv < 8);
+	const bool use_anyd = anyd_ok && (anyd == 2 || !old_ok);
+	if (!old_ok && !use_anyd) return CCV_NNC_EXEC_NO_KERNEL;
+	if (w && !sdpa_projection_ok(g, c, outputs[0], w, bias)) return CCV_NNC_EXEC_NO_KERNEL; // (the fp32 route answers)
 	if ((((uintptr_t)q->data.u8 | (uintptr_t)k->data.u8 | (uintptr_t)v->data.u8) & 15) || ((uintptr_t)c->data.u8 & 7)) return CCV_NNC_EXEC_NO_KERNEL;
 	if ((g.q_sb | g.q_sr | g.q_sh | g.k_sb | g.k_sc | g.k_sh | g.v_sb | g.v_sc | g.v_sh) & 7) return CCV_NNC_EXEC_NO_KERNEL;
 	if ((g.o_sb | g.o_sr | g.o_sh) & 3) return CCV_NNC_EXEC_NO_KERNEL;
@@ -1063,8 +1092,9 @@ static int sdpa_forw_half(EXEC_ARGS)
 	}
 	MarkerScope marker(cmd.cmd);
 	if (!g.R || !g.Hq || !g.B) return CCV_NNC_EXEC_SUCCESS;
-	sdpa_forw_f16_launch(g, (const half_t*)q->data.u8, (const half_t*)k->data.u8, (const half_t*)v->data.u8, mask ? (const half_t*)mask->data.u8 : 0, (half_t*)c->data.u8, lse, stream_of(stream_context));
-	return CCV_NNC_EXEC_SUCCESS;
+	(use_anyd ? sdpa_fwd_anyd_f16_launch : sdpa_forw_f16_launch)(g, (const half_t*)q->data.u8, (const half_t*)k->data.u8, (const half_t*)v->data.u8, mask ? (const half_t*)mask->data.u8 : 0, (half_t*)c->data.u8, lse, stream_of(stream_context));
+	if (!w) return CCV_NNC_EXEC_SUCCESS;
+	return sdpa_projection(g, c, outputs[0], w, bias, stream_context); // a GEMM_FORWARD on the half tensors: the f16 contraction core
 }
 // the registered forward entry: fp32 tensors -> the fp32 kernels; half q / k / v / o -> the f16 kernel where it applies; anything else with a half tensor -> the fp32
 // kernels on fp32 images (half_stage.cpp)
