@@ -901,6 +901,9 @@ __global__ void __launch_bounds__(256) sdpa_dkv_f16_kernel(const sdpa_geom_t g, 
 	}
 }
 
+// ---- backward in half precision for every head size in 8s up to 256: sdpa_bwd_anyd_dq_f16_kernel, sdpa_bwd_anyd_dkv_f16_kernel and their launcher ---------------
+#include "sdpa_anyd_f16_back.h"
+
 // ---- host -----------------------------------------------------------------------------------------------------------------------
 struct bhd_t { int b, n, h, d; long sb, sn, sh; };
 static bool bhd(const ccv_nnc_tensor_t* t, bhd_t* o, const int datatype = CCV_32F)
@@ -1194,7 +1197,8 @@ static int _sdpa_back(EXEC_ARGS)
 	return CCV_NNC_EXEC_SUCCESS;
 }
 
-// CCV_16F g / q / k / v -> dq / dk / dv: the f16 kernels where their conditions hold (CCV_NNC_EXEC_NO_KERNEL = not this path)
+// CCV_16F g / q / k / v -> dq / dk / dv: sdpa_dq_f16_kernel / sdpa_dkv_f16_kernel where their conditions hold, the kernels of sdpa_anyd_f16_back.h for the other
+// head sizes in 8s up to 256 (CCV_NNC_EXEC_NO_KERNEL = not this path)
 static int sdpa_back_half(EXEC_ARGS)
 {
 	if (input_size < 6 || output_size < 3 || !inputs[0] || !inputs[3] || !inputs[4] || !inputs[5]) return CCV_NNC_EXEC_NO_KERNEL;
@@ -1217,7 +1221,15 @@ static int sdpa_back_half(EXEC_ARGS)
 	if (dq && (!bhd(dq, &dqi, CCV_16F) || dqi.b != g.B || dqi.n != g.R || dqi.h != g.Hq || dqi.d != g.D)) return CCV_NNC_EXEC_NO_KERNEL;
 	if (dk && (!bhd(dk, &dki, CCV_16F) || dki.b != g.B || dki.n != g.C || dki.h != g.Hk || dki.d != g.D)) return CCV_NNC_EXEC_NO_KERNEL;
 	if (dv && (!bhd(dv, &dvi, CCV_16F) || dvi.b != g.B || dvi.n != g.C || dvi.h != g.Hk || dvi.d != g.Dv)) return CCV_NNC_EXEC_NO_KERNEL;
-	if (g.D % 32 || g.Dv % 32 || g.D > 128 || g.Dv > 128) return CCV_NNC_EXEC_NO_KERNEL;
+	// sdpa_dq_f16_kernel / sdpa_dkv_f16_kernel keep the shapes they take; the kernels of sdpa_anyd_f16_back.h take the others in 8s up to 256 (key SDPA_F16_ANYD:
+	// 0 = never, 2 = every shape they can, for measurements); the forward re-run is the kernel sdpa_forw_half picks for the shape
+	const long anyd = tune(TUNE_SDPA_F16_ANYD);
+	const bool old_ok = !(g.D % 32 || g.Dv % 32 || g.D > 128 || g.Dv > 128);
+	const bool anyd_ok = anyd && !(g.D % 8 || g.Dv % 8 || g.D > 256 || g.Dv > 256 || g.D < 8 || g.Dv < 8);
+	const bool use_anyd = anyd_ok && (anyd == 2 || !old_ok);
+	if (!old_ok && !use_anyd) return CCV_NNC_EXEC_NO_KERNEL;
+	const bool forw_old_ok = !(g.D % 16 || g.Dv % 32 || g.D > 128 || g.Dv > 128 || g.D < 16);
+	const bool forw_anyd = anyd_ok && (anyd == 2 || !forw_old_ok);
 	if (mask && !sdpa_mask_geometry(mask, &g, CCV_16F)) return CCV_NNC_EXEC_NO_KERNEL;
 	const half_t* const mp = mask ? (const half_t*)mask->data.u8 : 0;
 	if (((uintptr_t)q->data.u8 | (uintptr_t)k->data.u8 | (uintptr_t)v->data.u8 | (uintptr_t)inputs[0]->data.u8) & 15) return CCV_NNC_EXEC_NO_KERNEL;
@@ -1236,9 +1248,14 @@ static int sdpa_back_half(EXEC_ARGS)
 	sdpa_geom_t gf = g;
 	gf.o_sb = (long)g.R * g.Hq * g.Dv; gf.o_sr = (long)g.Hq * g.Dv; gf.o_sh = g.Dv;
 	const half_t* const qp = (const half_t*)q->data.u8; const half_t* const kp = (const half_t*)k->data.u8; const half_t* const vp = (const half_t*)v->data.u8; const half_t* const gp = (const half_t*)inputs[0]->data.u8;
-	sdpa_forw_f16_launch(gf, qp, kp, vp, mp, o, lse, stream);
+	(forw_anyd ? sdpa_fwd_anyd_f16_launch : sdpa_forw_f16_launch)(gf, qp, kp, vp, mp, o, lse, stream);
 	hipLaunchKernelGGL(sdpa_delta_h_kernel, dim3(grid_for(rows, 256)), dim3(256), 0, stream, g, gp, gi.sb, gi.sn, gi.sh, (const half_t*)o, delta);
 	HIP_ENFORCE(hipGetLastError());
+	if (use_anyd) {
+		sdpa_bwd_anyd_f16_launch(g, qp, kp, vp, mp, gp, gi.sb, gi.sn, gi.sh, (const float*)lse, (const float*)delta, dq ? (half_t*)dq->data.u8 : 0, dq ? dqi.sb : 0, dq ? dqi.sn : 0, dq ? dqi.sh : 0,
+			dk ? (half_t*)dk->data.u8 : 0, dk ? dki.sb : 0, dk ? dki.sn : 0, dk ? dki.sh : 0, dv ? (half_t*)dv->data.u8 : 0, dv ? dvi.sb : 0, dv ? dvi.sn : 0, dv ? dvi.sh : 0, stream);
+		return CCV_NNC_EXEC_SUCCESS;
+	}
 #define SDPA_BY_GS(KERNEL, DS, ...) do { switch (g.Dv / 32) { \
 		case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<DS, 2>), __VA_ARGS__); break; case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<DS, 4>), __VA_ARGS__); break; \
 		case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<DS, 6>), __VA_ARGS__); break; default: hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<DS, 8>), __VA_ARGS__); break; } } while (0)

@@ -283,7 +283,7 @@ enum {
 	TUNE_INDEX_BACK_TILES,  // INDEX_SELECT_BACKWARD on dense tensors, fp32 and half: a wave per tile of destination rows and columns sums its sources in row order in LDS and writes the tile once, zeros included (1), or zero_rows_kernel and index_scatter_add_kernel, one thread per column (0; a half command then keeps its fp32 images).  The sums are bit for bit the same
 	TUNE_CMUL_HALF_NATIVE,  // CMUL_FORWARD / CMUL_BACKWARD (rotary position embeddings) read and write dense CCV_16F tensors as halves themselves on the kernels of cmul_ops.h (1), or run on fp32 images of them (0)
 	TUNE_GRAD_HALF_NATIVE,  // whole-tensor REDUCE_NORM2_FORWARD and REDUCE_ISNAN_FORWARD of a dense CCV_16F tensor and MUL_FORWARD of one by a one-element tensor (gradient clipping and the NaN check of a half-precision trainer) read and write the halves themselves on the kernels of grad_ops.h (1), or run on fp32 images of them (0)
-	TUNE_SDPA_F16_ANYD,     // SCALED_DOT_PRODUCT_ATTENTION_FORWARD on CCV_16F tensors: head sizes sdpa_forw_f16_kernel refuses (D, Dv in 8s up to 256) and the head projection stay in half on sdpa_fwd_anyd_f16_kernel (sdpa_anyd_f16.h) and the f16 contraction core (1), or run on fp32 images (0); 2 = every eligible forward on the new kernel, sdpa_forw_f16_kernel's shapes included (measurements)
+	TUNE_SDPA_F16_ANYD,     // SCALED_DOT_PRODUCT_ATTENTION_FORWARD on CCV_16F tensors: head sizes sdpa_forw_f16_kernel refuses (D, Dv in 8s up to 256) and the head projection stay in half on sdpa_fwd_anyd_f16_kernel (sdpa_anyd_f16.h) and the f16 contraction core (1), or run on fp32 images (0); 2 = every eligible forward on the new kernel, sdpa_forw_f16_kernel's shapes included (measurements).  SCALED_DOT_PRODUCT_ATTENTION_BACKWARD follows the same key: head sizes sdpa_dq_f16_kernel / sdpa_dkv_f16_kernel refuse (D, Dv in 8s up to 256) run on sdpa_bwd_anyd_dq_f16_kernel / sdpa_bwd_anyd_dkv_f16_kernel (sdpa_anyd_f16_back.h) (1), or on fp32 images (0); 2 = every eligible backward on the new kernels
 	TUNE_COUNT
 };
 static_assert(TUNE_GRID_WG_PER_CU == 3, "grid_for() above names this key by value");

@@ -4,8 +4,10 @@ heads, causal), with D = 64 as the control (sdpa_forw_f16_kernel on both sides) 
 after a warm-up of every shape.  Per row: the median of `--repeats` windows of at least `--window-ms`, their spread (max - min) and the TFLOP/s of
 2 B Hq R C (D + Dv) products (halved for causal rows).  Uses nothing but the command interface, so it runs unchanged on a build without sdpa_fwd_anyd_f16_kernel
 (--lib): both sides of a comparison come from this script, run alternately, and --report lays the runs side by side.  --key2 adds, for information, rows with the
-tuning key SDPA_F16_ANYD at 2 (the new kernel on sdpa_forw_f16_kernel's shapes) at D = 64 and D = 128.
-usage: python tools/attention_heads_bench.py [--lib PATH] [--label NAME] [--repeats 11] [--window-ms 20] [--key2] [--json OUT]
+tuning key SDPA_F16_ANYD at 2 (the new kernel on sdpa_forw_f16_kernel's shapes) at D = 64 and D = 128.  --backward times ONE
+SCALED_DOT_PRODUCT_ATTENTION_BACKWARD (g, q, k, v -> dq, dk, dv) per row on the same shapes instead: the TFLOP/s are then those of the five backward products
+S, dP, dQ, dK, dV, 2 B Hq R C (3 D + 2 Dv) (the forward re-run inside the command is not counted as work).
+usage: python tools/attention_heads_bench.py [--backward] [--lib PATH] [--label NAME] [--repeats 11] [--window-ms 20] [--key2] [--json OUT]
        python tools/attention_heads_bench.py --report NEW1.json PARENT1.json [NEW2.json PARENT2.json]"""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,9 +39,11 @@ def measure(args):
 
     def command(shape):
         B, R, C, Hq, Hk, D, causal = shape
-        cmd = nnc.generic_cmd("SCALED_DOT_PRODUCT_ATTENTION_FORWARD")
+        cmd = nnc.generic_cmd("SCALED_DOT_PRODUCT_ATTENTION_BACKWARD" if args.backward else "SCALED_DOT_PRODUCT_ATTENTION_FORWARD")
         cmd.info.f1.v = float(1.0 / np.sqrt(D))       # scaled_dot_product_attention.scale
         cmd.info.blas.transpose_a[1] = int(causal)    # .is_causal
+        if args.backward:
+            return cmd, [dev(B, R, Hq, D), None, None, dev(B, R, Hq, D), dev(B, C, Hk, D), dev(B, C, Hk, D)], [dev(B, R, Hq, D), dev(B, C, Hk, D), dev(B, C, Hk, D)]
         return cmd, [dev(B, R, Hq, D), dev(B, C, Hk, D), dev(B, C, Hk, D)], [dev(B, R, Hq, D)]
 
     def window(cmd, ins, outs, reps):
@@ -73,20 +77,20 @@ def measure(args):
         reps = max(1, min(2000, int(args.window_ms / max(one, 1e-3)) + 1))
         ms = sorted(window(cmd, ins, outs, reps) for _ in range(max(1, args.repeats)))
         med, spread = ms[len(ms) // 2], ms[-1] - ms[0]
-        flop = 2.0 * B * Hq * R * C * 2 * D * (0.5 if causal else 1.0)
+        flop = 2.0 * B * Hq * R * C * (5 if args.backward else 2) * D * (0.5 if causal else 1.0)
         out.append(dict(row=name, ms=med, spread=spread, flop=flop, launches=launches[name]))
         print("%-44s %9.4f ms (%.4f) | %7.1f | %s" % (out[-1]["row"], med, spread, flop / med / 1e9, ",".join(launches[name])), flush=True)
     if args.key2:
         L.tune_set("SDPA_F16_ANYD", 1)
     if args.json:
         with open(args.json, "w") as f:
-            json.dump(dict(label=args.label, rows=out), f)
+            json.dump(dict(label=args.label, backward=args.backward, rows=out), f)
 
 
 def report(paths):
     runs = [json.load(open(p)) for p in paths]
     new, old = [r for r in runs if r["label"] != "parent"], [r for r in runs if r["label"] == "parent"]
-    print("Median ms (spread = max - min of the windows).  `TFLOP/s`: 2 B Hq R C (D + Dv), halved for causal rows, per second of this tree's slower run.  `parent spread`:")
+    print("Median ms (spread = max - min of the windows).  `TFLOP/s`: 2 B Hq R C %s, halved for causal rows, per second of this tree's slower run.  `parent spread`:" % ("(3 D + 2 Dv)" if runs[0].get("backward") else "(D + Dv)"))
     print("the largest of the parent's window spreads and the distance between its runs.  `margin`: (the parent's faster run - this tree's slower run) / parent spread;")
     print("a row counts as faster where it is above 2.\n")
     head = ["(B,R,C,Hq,Hk,D)"] + ["%s, run %d" % (lab, i + 1) for i in range(max(len(new), len(old))) for lab in ("this tree", "parent")][:len(runs)] + ["TFLOP/s", "parent TFLOP/s", "parent spread", "margin", "parent / this tree"]
@@ -116,6 +120,7 @@ def report(paths):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--backward", action="store_true", help="time SCALED_DOT_PRODUCT_ATTENTION_BACKWARD instead of the forward command")
     ap.add_argument("--lib", default=None, help="another build of libnnc_mi355x.so")
     ap.add_argument("--label", default="this tree", help="'parent' for the parent commit's build")
     ap.add_argument("--repeats", type=int, default=11, help="timed windows per row: the median and the spread are reported")
