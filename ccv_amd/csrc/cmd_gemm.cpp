@@ -4,6 +4,7 @@
 // lib/nnc/cmd/blas/gpu/ccv_nnc_gemm_gpu_cublas.cu:232-390, :616-795 -- the bias add is an epilogue of the contraction
 // instead of the reference's rank-1 GEMM with a ones vector (:158-162), and dbias is a column reduction (:421-431).
 #include "gemm_launch.h"
+#include "gemm_qx_f16.h"
 
 using namespace nnc;
 
@@ -271,6 +272,51 @@ static int gemm_back_any(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, con
 	return half_staged_exec(_gemm_back_f32, cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
 }
 
+// A 3-d operand whose batch entries follow each other at the row stride is one matrix of batch x rows rows.  false: an outer batch, or entries apart.
+static bool collapse_rows(matp_t<half_t>* const m)
+{
+	if (m->outer_nd) return false;
+	if (m->batch > 1 && m->batch_inc != (long)m->rows * m->rows_inc) return false;
+	m->rows *= m->batch; m->batch = 1;
+	return true;
+}
+// A dense layer (ccv_cnnp_dense: lib/nnc/ccv_cnnp_model_addons.c:1368-1373 issues GEMM_FORWARD with transpose_b = (0, 1) against w[N, K]) on at most
+// GEMM_QX_FUSED <= 32 half rows against a palettized weight with a half palette: gemm_qx_f16.h decodes the weight inside the contraction.  The operands it reads
+// 16 bytes at a time (a) or by groups of eight indices (w: K and number_in_blocks multiples of eight) are checked here; GEMM_QX_NOT_TAKEN = any other command.
+static int gemm_qx_fused(const ccv_nnc_cmd_t cmd, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
+{
+	long max_m = tune(TUNE_GEMM_QX_FUSED);
+	if (max_m > QX_MAX_M) max_m = QX_MAX_M;
+	if (max_m <= 0 || (flags & CCV_NNC_ACCUMULATE_OUTPUT) || input_size < 2 || output_size < 1 || !inputs[0] || !inputs[1] || !outputs[0]) return GEMM_QX_NOT_TAKEN;
+	const ccv_nnc_tensor_t* const a = inputs[0];
+	const ccv_nnc_tensor_t* const w = inputs[1];
+	const ccv_nnc_tensor_t* const bias = input_size > 2 ? inputs[2] : 0;
+	ccv_nnc_tensor_t* const b = outputs[0];
+	const int* const ta = cmd.info.blas.transpose_a;
+	const int* const tb = cmd.info.blas.transpose_b;
+	if (ta[0] != ta[1] || !((tb[0] == 0 && tb[1] == 1) || (tb[0] == 1 && tb[1] == 0))) return GEMM_QX_NOT_TAKEN;
+	if (CCV_GET_DATA_TYPE(w->info.datatype) != CCV_QX || ((w->info.datatype & 0xff) << 12) != CCV_16F || tensor_nd(w->info.dim) != 2) return GEMM_QX_NOT_TAKEN;
+	if (CCV_IS_TENSOR_VIEW(w) && !tensor_contiguous(w)) return GEMM_QX_NOT_TAKEN;
+	if (CCV_GET_DATA_TYPE(a->info.datatype) != CCV_16F || CCV_GET_DATA_TYPE(b->info.datatype) != CCV_16F || (bias && CCV_GET_DATA_TYPE(bias->info.datatype) != CCV_16F)) return GEMM_QX_NOT_TAKEN;
+	const int qbits = (w->info.datatype & 0xf00) >> 8, nib = w->info.reserved;
+	const int N = w->info.dim[0], K = w->info.dim[1];
+	if (qbits < 4 || qbits > 8 || nib <= 0 || nib % 8 || K <= 0 || K % 8 || N <= 0) return GEMM_QX_NOT_TAKEN;
+	matp_t<half_t> am, bm, sm;
+	if (!matrix_params(a, no_transpose, &am) || !matrix_params(b, no_transpose, &bm) || !collapse_rows(&am) || !collapse_rows(&bm)) return GEMM_QX_NOT_TAKEN;
+	if (am.cols != K || bm.cols != N || am.rows != bm.rows || am.rows < 1 || am.rows > max_m) return GEMM_QX_NOT_TAKEN;
+	if (am.cols_inc != 1 || am.rows_inc % 8 || ((uintptr_t)am.p & 15) || bm.cols_inc != 1) return GEMM_QX_NOT_TAKEN;
+	if (bias && (!matrix_params(bias, no_transpose, &sm) || sm.outer_nd || sm.batch != 1 || sm.rows != 1 || sm.cols != N || sm.cols_inc != 1)) return GEMM_QX_NOT_TAKEN;
+	MarkerScope marker(cmd.cmd);
+	return gemm_qx_f16_run(w->data.u8, qbits, nib, am.p, am.rows_inc, bias ? sm.p : 0, bm.p, bm.rows_inc, am.rows, N, K, stream_context);
+}
+// palettized a / w (ccv_nnc_gemm_gpu_cublas.cu:289-334): the fused kernel where it applies, else the dense command on expanded images (palette.cpp)
+static int _gemm_forw_qx(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
+{
+	const int taken = gemm_qx_fused(cmd, flags, inputs, input_size, outputs, output_size, stream_context);
+	if (taken != GEMM_QX_NOT_TAKEN) return taken;
+	return depalettized<_gemm_forw>(cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
+}
+
 } // namespace
 
 extern "C" void _register_command_CCV_NNC_GEMM_FORWARD_backend_CCV_NNC_BACKEND_GPU_CUBLAS(ccv_nnc_cmd_backend_registry_t* const registry)
@@ -281,6 +327,7 @@ extern "C" void _register_command_CCV_NNC_GEMM_FORWARD_backend_CCV_NNC_BACKEND_G
 	registry->algorithms = 1;
 	registry->exec = _gemm_forw;
 	NNC_DEPALETTIZED(registry, _gemm_forw); // palettized a / w (ccv_nnc_gemm_gpu_cublas.cu:289-334)
+	registry->exec = _gemm_forw_qx;         // ... with gemm_qx_f16.h in front of it for a dense layer's few rows
 }
 
 extern "C" void _register_command_CCV_NNC_GEMM_BACKWARD_backend_CCV_NNC_BACKEND_GPU_CUBLAS(ccv_nnc_cmd_backend_registry_t* const registry)

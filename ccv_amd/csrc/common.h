@@ -284,6 +284,8 @@ enum {
 	TUNE_CMUL_HALF_NATIVE,  // CMUL_FORWARD / CMUL_BACKWARD (rotary position embeddings) read and write dense CCV_16F tensors as halves themselves on the kernels of cmul_ops.h (1), or run on fp32 images of them (0)
 	TUNE_GRAD_HALF_NATIVE,  // whole-tensor REDUCE_NORM2_FORWARD and REDUCE_ISNAN_FORWARD of a dense CCV_16F tensor and MUL_FORWARD of one by a one-element tensor (gradient clipping and the NaN check of a half-precision trainer) read and write the halves themselves on the kernels of grad_ops.h (1), or run on fp32 images of them (0)
 	TUNE_SDPA_F16_ANYD,     // SCALED_DOT_PRODUCT_ATTENTION_FORWARD on CCV_16F tensors: head sizes sdpa_forw_f16_kernel refuses (D, Dv in 8s up to 256) and the head projection stay in half on sdpa_fwd_anyd_f16_kernel (sdpa_anyd_f16.h) and the f16 contraction core (1), or run on fp32 images (0); 2 = every eligible forward on the new kernel, sdpa_forw_f16_kernel's shapes included (measurements).  SCALED_DOT_PRODUCT_ATTENTION_BACKWARD follows the same key: head sizes sdpa_dq_f16_kernel / sdpa_dkv_f16_kernel refuse (D, Dv in 8s up to 256) run on sdpa_bwd_anyd_dq_f16_kernel / sdpa_bwd_anyd_dkv_f16_kernel (sdpa_anyd_f16_back.h) (1), or on fp32 images (0); 2 = every eligible backward on the new kernels
+	TUNE_GEMM_QX_FUSED,     // GEMM_FORWARD of CCV_16F rows against a CCV_QX weight [N, K] with a half palette (transpose_b: the dense layer's form) decodes the weight's index stream inside the contraction (gemm_qx_f16.h): the largest row count M that takes that kernel, at most 32; 0 = never (the weight is expanded to a dense image first, palette.cpp)
+	TUNE_GEMM_QX_SLICES,    // ... its slices of K: 0 = chosen by the launch, n = n slices (tests, measurements)
 	TUNE_COUNT
 };
 static_assert(TUNE_GRID_WG_PER_CU == 3, "grid_for() above names this key by value");
@@ -378,6 +380,8 @@ static int depalettized(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, cons
 {
 	return depalettized_exec(F, cmd, hint, flags, inputs, input_size, outputs, output_size, ctx);
 }
+// cmd_gemm.cpp in front of depalettized<_gemm_forw>: GEMM_QX_NOT_TAKEN = not a command gemm_qx_f16.h takes, nothing was launched (else CCV_NNC_EXEC_*)
+constexpr int GEMM_QX_NOT_TAKEN = 1;
 #define NNC_DEPALETTIZED(registry, EXEC) do { (registry)->tensor_datatypes |= CCV_QX; (registry)->exec = nnc::depalettized<EXEC>; } while (0)
 
 // Registration table (registry.cpp).

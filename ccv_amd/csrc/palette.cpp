@@ -24,6 +24,7 @@
 // (small blocks still slow); runs of blocks per workgroup 3.8 - 5.6 (floats low: a lane wrote 32 bytes as two stores 32 bytes apart); 16-byte shares: this.
 // A command that meets a CCV_QX input runs on a dense image of it: depalettized_exec() below.
 #include "common.h"
+#include "palette_bits.h"
 
 namespace nnc {
 namespace {
@@ -33,39 +34,7 @@ constexpr int PAL_GROUPS_PER_LANE = 4; // tasks a lane takes (PAL_THREADS apart)
 constexpr int PAL_CHUNK = PAL_THREADS * PAL_GROUPS_PER_LANE; // 16-byte shares of groups (tasks) per workgroup
 constexpr int PAL_LDS_BYTES = 16384;   // palettes a workgroup may stage: 8 runs of blocks per CU stay resident
 
-// index bytes of a FULL block, as the host's quantiser lays them out (ccv_nnc_palettize.c: the `ui0` strides of each bit width)
-__host__ __device__ __forceinline__ size_t index_bytes_per_block(const int qbits, const int nib)
-{
-	switch (qbits) {
-		case 4: return (size_t)(nib / 2);
-		case 5: return (size_t)(nib / 8) * 5;
-		case 6: return (size_t)(nib / 4) * 3;
-		case 7: return (size_t)(nib / 8) * 7;
-		default: return (size_t)nib;
-	}
-}
-
-// One group: up to eight elements starting at element 8 g of a block.  `idx` points at the group's first index byte, `valid` (1 .. 8) elements exist.
-// Fast path (a full group whose eight bytes idx[0 .. 7] all lie inside the stream -- every group but the stream's last one or two): ONE 8-byte load (gfx950
-// global loads need no alignment), a byte swap, and a constant shift + mask per element.  Otherwise byte by byte, and only the index bytes the group's
-// elements touch are read (the stream of the tensor's last block ends with them).
-template <int Q>
-__device__ __forceinline__ unsigned long long group_bits(const unsigned char* const idx, const int valid, const bool whole)
-{ // the group's Q bytes as one big-endian number in the TOP 8 Q bits of the result: element j = bits [64 - (j + 1) Q, 64 - j Q)
-	if (whole) {
-		unsigned long long raw;
-		__builtin_memcpy(&raw, idx, 8);
-		return __builtin_bswap64(raw);
-	}
-	const int nbytes = valid == 8 ? Q : (valid * Q + 7) >> 3;
-	unsigned long long w = 0;
-#pragma unroll
-	for (int i = 0; i < Q; i++) {
-		const unsigned long long b = i < nbytes ? idx[i] : 0;
-		w |= b << (8 * (7 - i));
-	}
-	return w;
-}
+// (index_bytes_per_block and group_bits, the stream's layout: palette_bits.h, shared with gemm_qx_f16.h)
 // A lane's share of a group: EPL = 16 / sizeof(ELEM) consecutive elements (8 halves, 4 floats, 2 doubles) -- ONE 16-byte store per lane, consecutive lanes
 // consecutive 16 bytes, whatever the element size.  `w` holds the lane's first element in its top Q bits, `valid` counts the lane's elements that exist.
 template <typename ELEM, int Q, typename LUT>
