@@ -338,6 +338,7 @@ __global__ void __launch_bounds__(256) sdpa_forw_f16_kernel(const sdpa_geom_t g,
 
 // ---- forward in half precision for every head size in 8s up to 256: sdpa_fwd_anyd_f16_kernel and its launcher ------------------------------------------------
 #include "sdpa_anyd_f16.h"
+#include "sdpa_decode_f16.h"
 
 // delta[b][h][x] = sum_d g[b, x, h, d] * o[b, x, h, d]   (o: the scratch copy, dense [B][R][Hq][Dv])
 __global__ void __launch_bounds__(256) sdpa_delta_kernel(const sdpa_geom_t g, const float* __restrict__ gr, const long g_sb, const long g_sr, const long g_sh, const float* __restrict__ o, float* __restrict__ delta)
@@ -1083,7 +1084,10 @@ static int sdpa_forw_half(EXEC_ARGS)
 	const bool old_ok = !(g.D % 16 || g.Dv % 32 || g.D > 128 || g.Dv > 128 || g.D < 16);
 	const bool anyd_ok = anyd && !(g.D % 8 || g.Dv % 8 || g.D > 256 || g.Dv > 256 || g.D < 8 || g.Dv < 8);
 	const bool use_anyd = anyd_ok && (anyd == 2 || !old_ok);
-	if (!old_ok && !use_anyd) return CCV_NNC_EXEC_NO_KERNEL;
+	// few query rows against a long cache: sdpa_decode_f16_kernel (sdpa_decode_f16.h) in front of both (key SDPA_F16_DECODE: 0 = never, n = from n keys on)
+	const long decode = tune(TUNE_SDPA_F16_DECODE);
+	const bool use_decode = decode > 0 && (long)g.R * g.ratio <= SDPA_DECODE_ROWS && g.C >= decode && !(g.D % 8 || g.Dv % 8 || g.D > 256 || g.Dv > 256 || g.D < 8 || g.Dv < 8);
+	if (!old_ok && !use_anyd && !use_decode) return CCV_NNC_EXEC_NO_KERNEL;
 	if (w && !sdpa_projection_ok(g, c, outputs[0], w, bias)) return CCV_NNC_EXEC_NO_KERNEL; // (the fp32 route answers)
 	if ((((uintptr_t)q->data.u8 | (uintptr_t)k->data.u8 | (uintptr_t)v->data.u8) & 15) || ((uintptr_t)c->data.u8 & 7)) return CCV_NNC_EXEC_NO_KERNEL;
 	if ((g.q_sb | g.q_sr | g.q_sh | g.k_sb | g.k_sc | g.k_sh | g.v_sb | g.v_sc | g.v_sh) & 7) return CCV_NNC_EXEC_NO_KERNEL;
@@ -1095,6 +1099,10 @@ static int sdpa_forw_half(EXEC_ARGS)
 	}
 	MarkerScope marker(cmd.cmd);
 	if (!g.R || !g.Hq || !g.B) return CCV_NNC_EXEC_SUCCESS;
+	if (use_decode) {
+		const int r = sdpa_decode_f16_run(g, (const half_t*)q->data.u8, (const half_t*)k->data.u8, (const half_t*)v->data.u8, mask ? (const half_t*)mask->data.u8 : 0, (half_t*)c->data.u8, lse, stream_context);
+		if (r != CCV_NNC_EXEC_SUCCESS) return r;
+	} else
 	(use_anyd ? sdpa_fwd_anyd_f16_launch : sdpa_forw_f16_launch)(g, (const half_t*)q->data.u8, (const half_t*)k->data.u8, (const half_t*)v->data.u8, mask ? (const half_t*)mask->data.u8 : 0, (half_t*)c->data.u8, lse, stream_of(stream_context));
 	if (!w) return CCV_NNC_EXEC_SUCCESS;
 	return sdpa_projection(g, c, outputs[0], w, bias, stream_context); // a GEMM_FORWARD on the half tensors: the f16 contraction core

@@ -286,6 +286,8 @@ enum {
 	TUNE_SDPA_F16_ANYD,     // SCALED_DOT_PRODUCT_ATTENTION_FORWARD on CCV_16F tensors: head sizes sdpa_forw_f16_kernel refuses (D, Dv in 8s up to 256) and the head projection stay in half on sdpa_fwd_anyd_f16_kernel (sdpa_anyd_f16.h) and the f16 contraction core (1), or run on fp32 images (0); 2 = every eligible forward on the new kernel, sdpa_forw_f16_kernel's shapes included (measurements).  SCALED_DOT_PRODUCT_ATTENTION_BACKWARD follows the same key: head sizes sdpa_dq_f16_kernel / sdpa_dkv_f16_kernel refuse (D, Dv in 8s up to 256) run on sdpa_bwd_anyd_dq_f16_kernel / sdpa_bwd_anyd_dkv_f16_kernel (sdpa_anyd_f16_back.h) (1), or on fp32 images (0); 2 = every eligible backward on the new kernels
 	TUNE_GEMM_QX_FUSED,     // GEMM_FORWARD of CCV_16F rows against a CCV_QX weight [N, K] with a half palette (transpose_b: the dense layer's form) decodes the weight's index stream inside the contraction (gemm_qx_f16.h): the largest row count M that takes that kernel, at most 32; 0 = never (the weight is expanded to a dense image first, palette.cpp)
 	TUNE_GEMM_QX_SLICES,    // ... its slices of K: 0 = chosen by the launch, n = n slices (tests, measurements)
+	TUNE_SDPA_F16_DECODE,   // SCALED_DOT_PRODUCT_ATTENTION_FORWARD on CCV_16F tensors with at most 32 packed rows (query rows x query heads per key head: the decode step) on the split-key kernel of sdpa_decode_f16.h: n > 0 = when the command has at least n keys (1 = every C), 0 = never (the other half forward kernels).  Default 256: faster than the former kernels on every measured row from C = 128 on, and no smaller than 256 so that short-cache shapes keep their kernels
+	TUNE_SDPA_DECODE_SPLITS, // ... its splits of the key axis: 0 = chosen by the launch, n = n splits (tests, measurements)
 	TUNE_COUNT
 };
 static_assert(TUNE_GRID_WG_PER_CU == 3, "grid_for() above names this key by value");
