@@ -17,6 +17,7 @@
 #include "common.h"
 #include "isa.h" // half_t, halfx8, nnc_mfma_f16
 #include <math.h>
+#include <type_traits> // std::integral_constant
 
 using namespace nnc;
 
@@ -32,6 +33,46 @@ struct sdpa_geom_t {
 	int causal;
 };
 constexpr int BR = 16; // query rows (forward, dq) / keys (dk, dv) per workgroup
+// values 8 t16 .. 8 t16 + 7 of a lane's sixteen (a float[16] or a floatx16), rounded to half: the B operand of sub-step t16 of a second product
+template <typename V>
+__device__ __forceinline__ halfx8 sdpa_half8(const V& v, const int t16)
+{
+	return halfx8{ (half_t)v[8 * t16], (half_t)v[8 * t16 + 1], (half_t)v[8 * t16 + 2], (half_t)v[8 * t16 + 3], (half_t)v[8 * t16 + 4], (half_t)v[8 * t16 + 5], (half_t)v[8 * t16 + 6], (half_t)v[8 * t16 + 7] };
+}
+
+// ---- what the host code below and the launchers of the sdpa_*.h files share --------------------------------------------------------
+struct bhd_t { int b, n, h, d; long sb, sn, sh; unsigned char* p; }; // a [B, N, H, D] tensor: sizes, element strides, data; all zeros: absent
+// the operands of the backward kernels behind the geometry: built once per command, unpacked by sdpa_launch_dq / sdpa_launch_dkv and nowhere else
+struct sdpa_back_ops_t {
+	const void *q, *k, *v, *mask;
+	bhd_t g, dq, dk, dv; // an absent gradient is all zeros
+	const float *lse, *delta; // the forward re-run's log-sum-exp, the row sums of g o
+};
+template <typename T, typename K> // T: float or half_t; K: a dq kernel
+static void sdpa_launch_dq(const K kernel, const dim3 grid, hipStream_t stream, const sdpa_geom_t& g, const sdpa_back_ops_t& a)
+{
+	hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, g, (const T*)a.q, (const T*)a.k, (const T*)a.v, (const T*)a.mask, (const T*)a.g.p, a.g.sb, a.g.sn, a.g.sh, a.lse, a.delta, (T*)a.dq.p, a.dq.sb, a.dq.sn, a.dq.sh);
+}
+template <typename T, typename K> // K: a dk / dv kernel
+static void sdpa_launch_dkv(const K kernel, const dim3 grid, hipStream_t stream, const sdpa_geom_t& g, const sdpa_back_ops_t& a)
+{
+	hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, g, (const T*)a.q, (const T*)a.k, (const T*)a.v, (const T*)a.mask, (const T*)a.g.p, a.g.sb, a.g.sn, a.g.sh, a.lse, a.delta, (T*)a.dk.p, a.dk.sb, a.dk.sn, a.dk.sh, (T*)a.dv.p, a.dv.sb, a.dv.sn, a.dv.sh);
+}
+// From a run-time size to a template instance.  A kernel family states its instances as ascending lists; sdpa_pick calls f(std::integral_constant<int, V>()) with
+// the first V of the list that v does not exceed (the last V where v exceeds them all): the list is the instance table, its gaps are the rounding rule.
+template <int... Vs> struct sdpa_ints {};
+template <int V, int... Vs, typename F>
+static void sdpa_pick(sdpa_ints<V, Vs...>, const int v, const F& f)
+{
+	if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V>());
+	else if (v <= V) f(std::integral_constant<int, V>());
+	else sdpa_pick(sdpa_ints<Vs...>(), v, f);
+}
+template <int... As, int... Bs, typename F> // f(A, B) over two lists
+static void sdpa_pick(sdpa_ints<As...> as, const int a, sdpa_ints<Bs...> bs, const int b, const F& f)
+{
+	sdpa_pick(as, a, [&](auto x) { sdpa_pick(bs, b, [&](auto y) { f(x, y); }); });
+}
 
 __device__ __forceinline__ float group16_max(float v) { for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64)); return v; }
 __device__ __forceinline__ float group16_sum(float v) { for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64); return v; }
@@ -121,7 +162,7 @@ __global__ void __launch_bounds__(256) sdpa_forw_kernel(const sdpa_geom_t g, con
 //   D layout: lane (row = l & 31, half = l >> 5) holds the keys ky(r) = (r & 3) + 8 (r >> 2) + 4 half of ITS row: maximum and sum are 16 registers + one swap
 //   O^T [Dv x 32 rows] += V^T P^T        MFMA j contracts the keys ky(j) (lanes 0-31) and ky(j) + 4 (lanes 32-63): its B operand IS register j of P^T -- the
 //                                        probabilities never leave the registers they were computed in; A = V[key][dv = l & 31] out of LDS
-// Conditions (sdpa_forward_launch): D % 8 == 0, Dv % 32 == 0, both <= 128, 16-byte aligned rows; everything else takes the kernel above.
+// Conditions (sdpa_route_fp32): D % 8 == 0, Dv % 32 == 0, both <= 128, 16-byte aligned rows; everything else takes the kernel above.
 template <int DH, int TV> // DH = D / 2 rounded up to the instantiation (32 or 64), TV = Dv / 32 (1 .. 4)
 __global__ void __launch_bounds__(256) sdpa_forw_mfma_kernel(const sdpa_geom_t g, const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, const float* __restrict__ mask, float* __restrict__ o, float* __restrict__ lse)
 {
@@ -315,7 +356,7 @@ __global__ void __launch_bounds__(256) sdpa_forw_f16_kernel(const sdpa_geom_t g,
 			for (int r = 0; r < 16; r++) acc[tv][r] *= alpha;
 #pragma unroll
 		for (int tt = 0; tt < 2; tt++) {
-			const halfx8 pf = halfx8{ (half_t)s[8 * tt], (half_t)s[8 * tt + 1], (half_t)s[8 * tt + 2], (half_t)s[8 * tt + 3], (half_t)s[8 * tt + 4], (half_t)s[8 * tt + 5], (half_t)s[8 * tt + 6], (half_t)s[8 * tt + 7] };
+			const halfx8 pf = sdpa_half8(s, tt);
 #pragma unroll
 			for (int tv = 0; tv < TV; tv++) {
 				const half_t* const vrow = Vt + (32 * tv + li) * VTP + 16 * tt + 4 * lh;
@@ -741,10 +782,6 @@ __device__ __forceinline__ halfx8 sdpa_tfrag(const half_t* const tt, const int c
 	const halfx4 lo = *(const halfx4*)p, hi = *(const halfx4*)(p + 8);
 	return halfx8{ lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3] };
 }
-__device__ __forceinline__ halfx8 sdpa_half8(const float (&v)[16], const int t16)
-{
-	return halfx8{ (half_t)v[8 * t16], (half_t)v[8 * t16 + 1], (half_t)v[8 * t16 + 2], (half_t)v[8 * t16 + 3], (half_t)v[8 * t16 + 4], (half_t)v[8 * t16 + 5], (half_t)v[8 * t16 + 6], (half_t)v[8 * t16 + 7] };
-}
 // 32 rows x COLS halves of a [rows][stride] tensor into a row-major tile (pitch COLS + 8) and, when tt != 0, its transpose ([column][40]); rows >= limit read as zeros
 template <int COLS>
 __device__ __forceinline__ void sdpa_stage_h(const half_t* const src, const long row_stride, const int first, const int limit, half_t* const rm, half_t* const tt, const int t)
@@ -906,71 +943,85 @@ __global__ void __launch_bounds__(256) sdpa_dkv_f16_kernel(const sdpa_geom_t g, 
 #include "sdpa_anyd_f16_back.h"
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-struct bhd_t { int b, n, h, d; long sb, sn, sh; };
-static bool bhd(const ccv_nnc_tensor_t* t, bhd_t* o, const int datatype = CCV_32F)
+static bool bhd(const ccv_nnc_tensor_t* t, bhd_t* o, const int datatype)
 { // [B, N, H, D] or [B, N, D]; D contiguous
 	const int nd = tensor_nd(t->info.dim);
 	if ((nd != 3 && nd != 4) || CCV_GET_DATA_TYPE(t->info.datatype) != datatype) return false;
 	int st[CCV_NNC_MAX_DIM_ALLOC];
 	tensor_strides(t, st);
 	if (st[nd - 1] != 1) return false;
-	o->b = t->info.dim[0]; o->n = t->info.dim[1]; o->sb = st[0]; o->sn = st[1];
+	o->b = t->info.dim[0]; o->n = t->info.dim[1]; o->sb = st[0]; o->sn = st[1]; o->p = t->data.u8;
 	if (nd == 4) { o->h = t->info.dim[2]; o->d = t->info.dim[3]; o->sh = st[2]; }
 	else { o->h = 1; o->d = t->info.dim[2]; o->sh = 0; }
 	return true;
 }
-static bool sdpa_mask_geometry(const ccv_nnc_tensor_t* mask, sdpa_geom_t* g, int datatype);
-static bool sdpa_geometry(const ccv_nnc_cmd_t& cmd, const ccv_nnc_tensor_t* q, const ccv_nnc_tensor_t* k, const ccv_nnc_tensor_t* v, const ccv_nnc_tensor_t* mask, sdpa_geom_t* g, bhd_t* qi, bhd_t* ki, bhd_t* vi)
+static bool bhd_is(const bhd_t& t, const int b, const int n, const int h, const int d) { return t.b == b && t.n == n && t.h == h && t.d == d; }
+// every row of t starts on a multiple of `bytes` (elements of `esize` bytes); an absent tensor passes
+static bool bhd_chunks(const bhd_t& t, const int bytes, const int esize) { return !((uintptr_t)t.p & (bytes - 1)) && !((t.sb | t.sn | t.sh) & (bytes / esize - 1)); }
+static bool sdpa_mask_geometry(const ccv_nnc_tensor_t* const mask, sdpa_geom_t* const g, const int datatype)
+{ // [B or 1][Hq or 1][R][C], or 3-d [B or 1][R][C]
+	const int nd = tensor_nd(mask->info.dim);
+	if ((nd != 3 && nd != 4) || CCV_GET_DATA_TYPE(mask->info.datatype) != datatype) return false;
+	int st[CCV_NNC_MAX_DIM_ALLOC];
+	tensor_strides(mask, st);
+	if (st[nd - 1] != 1 || mask->info.dim[nd - 1] != g->C || mask->info.dim[nd - 2] != g->R) return false;
+	g->m_sr = st[nd - 2];
+	const int mb = mask->info.dim[0], mh = nd == 4 ? mask->info.dim[1] : 1;
+	if ((mb != 1 && mb != g->B) || (mh != 1 && mh != g->Hq)) return false;
+	g->m_sb = mb == 1 ? 0 : st[0];
+	g->m_sh = (nd == 4 && mh != 1) ? st[1] : 0;
+	return true;
+}
+// The problem of a command, for all four entries: q / k / v / mask of `datatype` -> g (all but the output strides, which are the caller's) and the three bhd_t.
+// What is refused comes back in the order the entries answer it: SDPA_NO_QKV before the caller has anything to compare its own tensors with, SDPA_NO_MASK_OR_SIZE
+// with the sizes of g filled in.  The fp32 entries turn either into CCV_NNC_EXEC_INVALID, the half entries into CCV_NNC_EXEC_NO_KERNEL (the fp32 images answer).
+enum { SDPA_PARSED = 0, SDPA_NO_QKV, SDPA_NO_MASK_OR_SIZE };
+static int sdpa_geometry(const ccv_nnc_cmd_t& cmd, const ccv_nnc_tensor_t* q, const ccv_nnc_tensor_t* k, const ccv_nnc_tensor_t* v, const ccv_nnc_tensor_t* mask, const int datatype, sdpa_geom_t* g, bhd_t* qi, bhd_t* ki, bhd_t* vi)
 {
-	if (!bhd(q, qi) || !bhd(k, ki) || !bhd(v, vi)) return false;
-	if (tensor_nd(q->info.dim) != tensor_nd(k->info.dim) || tensor_nd(k->info.dim) != tensor_nd(v->info.dim)) return false;
-	if (qi->b != ki->b || ki->b != vi->b || qi->d != ki->d || ki->n != vi->n || ki->h != vi->h || qi->h < ki->h || qi->h % ki->h) return false;
+	memset(g, 0, sizeof(*g));
+	if (!bhd(q, qi, datatype) || !bhd(k, ki, datatype) || !bhd(v, vi, datatype)) return SDPA_NO_QKV;
+	if (tensor_nd(q->info.dim) != tensor_nd(k->info.dim) || tensor_nd(k->info.dim) != tensor_nd(v->info.dim)) return SDPA_NO_QKV;
+	if (qi->b != ki->b || ki->b != vi->b || qi->d != ki->d || ki->n != vi->n || ki->h != vi->h || qi->h < ki->h || qi->h % ki->h) return SDPA_NO_QKV;
 	g->B = qi->b; g->R = qi->n; g->C = ki->n; g->Hq = qi->h; g->Hk = ki->h; g->D = qi->d; g->Dv = vi->d; g->ratio = qi->h / ki->h;
 	g->q_sb = qi->sb; g->q_sr = qi->sn; g->q_sh = qi->sh; g->k_sb = ki->sb; g->k_sc = ki->sn; g->k_sh = ki->sh; g->v_sb = vi->sb; g->v_sc = vi->sn; g->v_sh = vi->sh;
-	g->m_sb = g->m_sh = g->m_sr = 0;
-	if (mask && !sdpa_mask_geometry(mask, g, CCV_32F)) return false;
 	g->scale = cmd.info.scaled_dot_product_attention.scale;
 	g->causal = cmd.info.scaled_dot_product_attention.is_causal;
-	return g->D >= 1 && g->Dv >= 1 && g->D <= 256 && g->Dv <= 256;
+	if (mask && !sdpa_mask_geometry(mask, g, datatype)) return SDPA_NO_MASK_OR_SIZE;
+	return g->D >= 1 && g->Dv >= 1 && g->D <= 256 && g->Dv <= 256 ? SDPA_PARSED : SDPA_NO_MASK_OR_SIZE;
 }
-static bool sdpa_mask_geometry(const ccv_nnc_tensor_t* const mask, sdpa_geom_t* const g, const int datatype)
+// dq / dk / dv of a backward command into a: each absent or of `datatype` and the sizes of q / k / v
+static bool sdpa_gradients(const sdpa_geom_t& g, ccv_nnc_tensor_t* const* const outputs, const int datatype, sdpa_back_ops_t* const a)
 {
-	{ // [B or 1][Hq or 1][R][C], or 3-d [B or 1][R][C]
-		const int nd = tensor_nd(mask->info.dim);
-		if ((nd != 3 && nd != 4) || CCV_GET_DATA_TYPE(mask->info.datatype) != datatype) return false;
-		int st[CCV_NNC_MAX_DIM_ALLOC];
-		tensor_strides(mask, st);
-		if (st[nd - 1] != 1 || mask->info.dim[nd - 1] != g->C || mask->info.dim[nd - 2] != g->R) return false;
-		g->m_sr = st[nd - 2];
-		const int mb = mask->info.dim[0], mh = nd == 4 ? mask->info.dim[1] : 1;
-		if ((mb != 1 && mb != g->B) || (mh != 1 && mh != g->Hq)) return false;
-		g->m_sb = mb == 1 ? 0 : st[0];
-		g->m_sh = (nd == 4 && mh != 1) ? st[1] : 0;
+	bhd_t* const o[3] = { &a->dq, &a->dk, &a->dv };
+	for (int i = 0; i < 3; i++) {
+		memset(o[i], 0, sizeof(bhd_t));
+		if (outputs[i] && (!bhd(outputs[i], o[i], datatype) || !bhd_is(*o[i], g.B, i ? g.C : g.R, i ? g.Hk : g.Hq, i < 2 ? g.D : g.Dv))) return false;
 	}
 	return true;
 }
-static int sdpa_forward_launch(const sdpa_geom_t& g, const float* q, const float* k, const float* v, const float* mask, float* o, float* lse, hipStream_t stream)
+// the output of a backward command's forward re-run: dense [B, R, Hq, Dv] in the workspace
+static sdpa_geom_t sdpa_rerun_geometry(sdpa_geom_t g) { g.o_sb = (long)g.R * g.Hq * g.Dv; g.o_sr = (long)g.Hq * g.Dv; g.o_sh = g.Dv; return g; }
+
+// ---- fp32: which of the three passes run on the matrix cores (the others: the VALU kernels) -----------------------------------------
+struct sdpa_route_fp32_t { bool forw, dq, dkv; };
+static sdpa_route_fp32_t sdpa_route_fp32(const sdpa_geom_t& g, const bhd_t& qi, const bhd_t& ki, const bhd_t& vi, const bhd_t* const gi)
+{
+	// whole 16-byte chunks of every row a kernel reads (gi: the backward's, 0 in the forward command), the output a whole number of MFMA tiles
+	const bool rows16 = bhd_chunks(qi, 16, 4) && bhd_chunks(ki, 16, 4) && bhd_chunks(vi, 16, 4);
+	const bool mfma = tune(TUNE_SDPA_MFMA) && rows16 && g.D <= 128 && g.Dv <= 128, back = mfma && gi && bhd_chunks(*gi, 16, 4) && g.D % 32 == 0;
+	return { mfma && g.D % 8 == 0 && g.Dv % 32 == 0, back && g.Dv % 8 == 0, back && g.Dv % 32 == 0 };
+}
+static int sdpa_forward_launch(const sdpa_geom_t& g, const bool mfma, const float* q, const float* k, const float* v, const float* mask, float* o, float* lse, hipStream_t stream)
 {
 	if (!g.R || !g.Hq || !g.B) return CCV_NNC_EXEC_SUCCESS;
-	// the matrix-core kernel: whole 16-byte chunks of q / k / v rows, the output tile a whole number of MFMA tiles
-	const bool rows16 = !(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) && !((g.q_sb | g.q_sr | g.q_sh | g.k_sb | g.k_sc | g.k_sh | g.v_sb | g.v_sc | g.v_sh) & 3);
-	if (tune(TUNE_SDPA_MFMA) && rows16 && g.D % 8 == 0 && g.Dv % 32 == 0 && g.D <= 128 && g.Dv <= 128) {
+	if (mfma) {
 		const dim3 grid((g.R + 127) / 128, g.Hq, g.B);
-		const int tv = g.Dv / 32;
 		// (both products of every (row, key) pair; causal masks skip key blocks, so this is an upper bound there)
 		ProfScope prof("sdpa_fwd|nnc::sdpa_forw_mfma_kernel", 2.0 * g.B * g.Hq * (double)g.R * g.C * (g.D + g.Dv), 0, g.R, g.C, g.D, g.B * g.Hq, 1, stream);
-#define SDPA_MFMA(DH, TV) hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_forw_mfma_kernel<DH, TV>), grid, dim3(256), 0, stream, g, q, k, v, mask, o, lse)
-		if (g.D <= 64) { if (tv == 1) SDPA_MFMA(32, 1); else if (tv == 2) SDPA_MFMA(32, 2); else if (tv == 3) SDPA_MFMA(32, 3); else SDPA_MFMA(32, 4); }
-		else { if (tv == 1) SDPA_MFMA(64, 1); else if (tv == 2) SDPA_MFMA(64, 2); else if (tv == 3) SDPA_MFMA(64, 3); else SDPA_MFMA(64, 4); }
-#undef SDPA_MFMA
-		HIP_ENFORCE(hipGetLastError());
-		return CCV_NNC_EXEC_SUCCESS;
-	}
-	const dim3 grid((g.R + BR - 1) / BR, g.Hq, g.B);
-	const int dm = g.D > g.Dv ? g.D : g.Dv;
-	if (dm <= 64) hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_forw_kernel<64, 64>), grid, dim3(256), 0, stream, g, q, k, v, mask, o, lse);
-	else if (dm <= 128) hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_forw_kernel<128, 32>), grid, dim3(256), 0, stream, g, q, k, v, mask, o, lse);
-	else hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_forw_kernel<256, 16>), grid, dim3(256), 0, stream, g, q, k, v, mask, o, lse);
+		sdpa_pick(sdpa_ints<32, 64>(), g.D / 2, sdpa_ints<1, 2, 3, 4>(), g.Dv / 32, [&](auto dh, auto tv) { // D / 2 rounded up to 32 or 64, Dv / 32
+			hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_forw_mfma_kernel<decltype(dh)::value, decltype(tv)::value>), grid, dim3(256), 0, stream, g, q, k, v, mask, o, lse); });
+	} else sdpa_pick(sdpa_ints<64, 128, 256>(), g.D > g.Dv ? g.D : g.Dv, [&](auto dmax) { // the LDS layout: 4096 floats a tile
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_forw_kernel<decltype(dmax)::value, 4096 / decltype(dmax)::value>), dim3((g.R + BR - 1) / BR, g.Hq, g.B), dim3(256), 0, stream, g, q, k, v, mask, o, lse); });
 	HIP_ENFORCE(hipGetLastError());
 	return CCV_NNC_EXEC_SUCCESS;
 }
@@ -989,15 +1040,14 @@ static int _sdpa_forw(EXEC_ARGS)
 	if (!c) return CCV_NNC_EXEC_INVALID;
 	sdpa_geom_t g;
 	bhd_t qi, ki, vi, ci;
-	if (!sdpa_geometry(cmd, inputs[0], inputs[1], inputs[2], mask, &g, &qi, &ki, &vi) || !bhd(c, &ci)) return CCV_NNC_EXEC_INVALID;
-	if (ci.b != g.B || ci.n != g.R || ci.h != g.Hq || ci.d != g.Dv) return CCV_NNC_EXEC_INVALID;
+	if (sdpa_geometry(cmd, inputs[0], inputs[1], inputs[2], mask, CCV_32F, &g, &qi, &ki, &vi) || !bhd(c, &ci, CCV_32F) || !bhd_is(ci, g.B, g.R, g.Hq, g.Dv)) return CCV_NNC_EXEC_INVALID;
 	g.o_sb = ci.sb; g.o_sr = ci.sn; g.o_sh = ci.sh;
 	float* lse = 0;
 	if (lse_t) {
 		if (CCV_GET_DATA_TYPE(lse_t->info.datatype) != CCV_32F || !tensor_contiguous(lse_t) || tensor_count(lse_t->info) != (size_t)g.B * g.Hq * g.R) return CCV_NNC_EXEC_INVALID;
 		lse = lse_t->data.f32;
 	}
-	int ret = sdpa_forward_launch(g, inputs[0]->data.f32, inputs[1]->data.f32, inputs[2]->data.f32, mask ? mask->data.f32 : 0, c->data.f32, lse, stream_of(stream_context));
+	int ret = sdpa_forward_launch(g, sdpa_route_fp32(g, qi, ki, vi, 0).forw, inputs[0]->data.f32, inputs[1]->data.f32, inputs[2]->data.f32, mask ? mask->data.f32 : 0, c->data.f32, lse, stream_of(stream_context));
 	if (ret != CCV_NNC_EXEC_SUCCESS || !w) return ret;
 	if (!sdpa_projection_ok(g, c, outputs[0], w, bias)) return CCV_NNC_EXEC_INVALID;
 	return sdpa_projection(g, c, outputs[0], w, bias, stream_context);
@@ -1030,68 +1080,61 @@ static int sdpa_projection(const sdpa_geom_t& g, ccv_nnc_tensor_t* const c, ccv_
 	return nnc_mi355x_cmd_exec(gemm, no_hint, 0, gin, bias ? 3 : 2, gout, 1, stream_context);
 }
 
+// ---- half: which kernel family takes the forward pass and which the backward --------------------------------------------------------
+// SDPA_F16: sdpa_forw_f16_kernel / sdpa_dq_f16_kernel + sdpa_dkv_f16_kernel, which keep the shapes they take; SDPA_ANYD: the kernels of sdpa_anyd_f16.h /
+// sdpa_anyd_f16_back.h for the other head sizes in 8s up to 256 (key SDPA_F16_ANYD: 0 = never, 2 = every shape they can, for measurements); SDPA_DECODE: few query
+// rows against a long cache on sdpa_decode_f16_kernel, in front of both (key SDPA_F16_DECODE: 0 = never, n = from n keys on), forward only and only where the
+// caller allows it: a backward command's forward re-run does not.  chunks: every row read is whole 16-byte chunks, every row written whole 8-byte chunks.
+// SDPA_NONE: not on these kernels (the caller goes through fp32 images).
+enum { SDPA_NONE = 0, SDPA_F16, SDPA_ANYD, SDPA_DECODE };
+struct sdpa_route_t { int forw, back; };
+static sdpa_route_t sdpa_route_half(const sdpa_geom_t& g, const bool chunks, const bool decode_allowed)
+{
+	if (!chunks) return { SDPA_NONE, SDPA_NONE };
+	const long anyd = tune(TUNE_SDPA_F16_ANYD), decode = tune(TUNE_SDPA_F16_DECODE);
+	const bool in8s = !(g.D % 8 || g.Dv % 8); // (1 .. 256: sdpa_geometry)
+	const bool forw_f16 = !(g.D % 16 || g.Dv % 32 || g.D > 128 || g.Dv > 128), back_f16 = forw_f16 && g.D % 32 == 0;
+	const auto family = [&](const bool f16) { return anyd && in8s && (anyd == 2 || !f16) ? SDPA_ANYD : f16 ? SDPA_F16 : SDPA_NONE; };
+	const bool use_decode = decode_allowed && decode > 0 && in8s && (long)g.R * g.ratio <= SDPA_DECODE_ROWS && g.C >= decode;
+	return { use_decode ? SDPA_DECODE : family(forw_f16), family(back_f16) };
+}
 static void sdpa_forw_f16_launch(const sdpa_geom_t& g, const half_t* const qp, const half_t* const kp, const half_t* const vp, const half_t* const mp, half_t* const op, float* const lse, hipStream_t stream)
 {
 	const dim3 grid((g.R + 127) / 128, g.Hq, g.B);
 	note_kernel("sdpa_fwd_f16");
 	ProfScope prof("sdpa_fwd_h|nnc::sdpa_forw_f16_kernel", 2.0 * g.B * g.Hq * (double)g.R * g.C * (g.D + g.Dv), 0, g.R, g.C, g.D, g.B * g.Hq, 1, stream);
-#define SDPA_F16_TV(DS) do { switch (g.Dv / 32) { \
-		case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_forw_f16_kernel<DS, 1>), grid, dim3(256), 0, stream, g, qp, kp, vp, mp, op, lse); break; \
-		case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_forw_f16_kernel<DS, 2>), grid, dim3(256), 0, stream, g, qp, kp, vp, mp, op, lse); break; \
-		case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_forw_f16_kernel<DS, 3>), grid, dim3(256), 0, stream, g, qp, kp, vp, mp, op, lse); break; \
-		default: hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_forw_f16_kernel<DS, 4>), grid, dim3(256), 0, stream, g, qp, kp, vp, mp, op, lse); break; } } while (0)
-	switch (g.D / 16) {
-		case 1: SDPA_F16_TV(1); break; case 2: SDPA_F16_TV(2); break; case 3: SDPA_F16_TV(3); break; case 4: SDPA_F16_TV(4); break;
-		case 5: SDPA_F16_TV(5); break; case 6: SDPA_F16_TV(6); break; case 7: SDPA_F16_TV(7); break; default: SDPA_F16_TV(8); break;
-	}
-#undef SDPA_F16_TV
+	sdpa_pick(sdpa_ints<1, 2, 3, 4, 5, 6, 7, 8>(), g.D / 16, sdpa_ints<1, 2, 3, 4>(), g.Dv / 32, [&](auto ds, auto tv) {
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_forw_f16_kernel<decltype(ds)::value, decltype(tv)::value>), grid, dim3(256), 0, stream, g, qp, kp, vp, mp, op, lse); });
 	HIP_ENFORCE(hipGetLastError());
 }
-// CCV_16F tensors: sdpa_forw_f16_kernel where its conditions hold, sdpa_fwd_anyd_f16_kernel for the other head sizes in 8s up to 256, the head projection as a half
-// GEMM_FORWARD behind either (CCV_NNC_EXEC_NO_KERNEL = not this path: the caller goes through fp32 images)
+// CCV_16F tensors: the forward family of sdpa_route_half, the head projection as a half GEMM_FORWARD behind it (CCV_NNC_EXEC_NO_KERNEL = not this path: the caller
+// goes through fp32 images)
 static int sdpa_forw_half(EXEC_ARGS)
 {
 	if (input_size < 3 || output_size < 1 || !inputs[0] || !inputs[1] || !inputs[2] || !outputs[0]) return CCV_NNC_EXEC_NO_KERNEL;
-	const long anyd = tune(TUNE_SDPA_F16_ANYD);
 	// the head projection: w, bias and both outputs CCV_16F too (mixed types, and every projection with the key at 0: the fp32 route)
 	const ccv_nnc_tensor_t* const w = input_size > 4 ? inputs[4] : 0;
 	const ccv_nnc_tensor_t* const bias = input_size > 5 ? inputs[5] : 0;
 	for (int i = 6; i < input_size; i++) if (inputs[i]) return CCV_NNC_EXEC_NO_KERNEL;
 	for (int i = 3; i < output_size; i++) if (outputs[i]) return CCV_NNC_EXEC_NO_KERNEL;
 	if (w) {
-		if (!anyd || output_size < 3 || !outputs[2] || CCV_GET_DATA_TYPE(w->info.datatype) != CCV_16F || (bias && CCV_GET_DATA_TYPE(bias->info.datatype) != CCV_16F) || CCV_GET_DATA_TYPE(outputs[0]->info.datatype) != CCV_16F) return CCV_NNC_EXEC_NO_KERNEL;
+		if (!tune(TUNE_SDPA_F16_ANYD) || output_size < 3 || !outputs[2] || CCV_GET_DATA_TYPE(w->info.datatype) != CCV_16F || (bias && CCV_GET_DATA_TYPE(bias->info.datatype) != CCV_16F) || CCV_GET_DATA_TYPE(outputs[0]->info.datatype) != CCV_16F) return CCV_NNC_EXEC_NO_KERNEL;
 	} else if (bias || (output_size > 2 && outputs[2])) return CCV_NNC_EXEC_NO_KERNEL;
 	const ccv_nnc_tensor_t* const mask = input_size > 3 ? inputs[3] : 0;
 	if (!tune(TUNE_SDPA_MFMA)) return CCV_NNC_EXEC_NO_KERNEL;
 	const ccv_nnc_tensor_t* const q = inputs[0]; const ccv_nnc_tensor_t* const k = inputs[1]; const ccv_nnc_tensor_t* const v = inputs[2];
 	ccv_nnc_tensor_t* const c = w ? outputs[2] : outputs[0];
 	ccv_nnc_tensor_t* const lse_t = output_size > 1 ? outputs[1] : 0;
-	bhd_t qi, ki, vi, ci;
-	if (!bhd(q, &qi, CCV_16F) || !bhd(k, &ki, CCV_16F) || !bhd(v, &vi, CCV_16F) || !bhd(c, &ci, CCV_16F)) return CCV_NNC_EXEC_NO_KERNEL;
-	if (tensor_nd(q->info.dim) != tensor_nd(k->info.dim) || tensor_nd(k->info.dim) != tensor_nd(v->info.dim)) return CCV_NNC_EXEC_NO_KERNEL;
-	if (qi.b != ki.b || ki.b != vi.b || qi.d != ki.d || ki.n != vi.n || ki.h != vi.h || qi.h < ki.h || qi.h % ki.h) return CCV_NNC_EXEC_NO_KERNEL;
 	sdpa_geom_t g;
-	memset(&g, 0, sizeof(g));
-	g.B = qi.b; g.R = qi.n; g.C = ki.n; g.Hq = qi.h; g.Hk = ki.h; g.D = qi.d; g.Dv = vi.d; g.ratio = qi.h / ki.h;
-	g.q_sb = qi.sb; g.q_sr = qi.sn; g.q_sh = qi.sh; g.k_sb = ki.sb; g.k_sc = ki.sn; g.k_sh = ki.sh; g.v_sb = vi.sb; g.v_sc = vi.sn; g.v_sh = vi.sh;
-	g.scale = cmd.info.scaled_dot_product_attention.scale;
-	g.causal = cmd.info.scaled_dot_product_attention.is_causal;
-	if (ci.b != g.B || ci.n != g.R || ci.h != g.Hq || ci.d != g.Dv) return CCV_NNC_EXEC_INVALID;
+	bhd_t qi, ki, vi, ci;
+	const int parsed = sdpa_geometry(cmd, q, k, v, mask, CCV_16F, &g, &qi, &ki, &vi);
+	if (parsed == SDPA_NO_QKV || !bhd(c, &ci, CCV_16F)) return CCV_NNC_EXEC_NO_KERNEL;
+	if (!bhd_is(ci, g.B, g.R, g.Hq, g.Dv)) return CCV_NNC_EXEC_INVALID; // (in front of the mask's and the sizes' refusal)
+	if (parsed != SDPA_PARSED) return CCV_NNC_EXEC_NO_KERNEL;
 	g.o_sb = ci.sb; g.o_sr = ci.sn; g.o_sh = ci.sh;
-	if (mask && !sdpa_mask_geometry(mask, &g, CCV_16F)) return CCV_NNC_EXEC_NO_KERNEL;
-	// sdpa_forw_f16_kernel keeps the shapes it takes; sdpa_fwd_anyd_f16_kernel (sdpa_anyd_f16.h) takes the others in 8s up to 256 (key SDPA_F16_ANYD: 0 = never,
-	// 2 = every shape it can, for measurements)
-	const bool old_ok = !(g.D % 16 || g.Dv % 32 || g.D > 128 || g.Dv > 128 || g.D < 16);
-	const bool anyd_ok = anyd && !(g.D % 8 || g.Dv % 8 || g.D > 256 || g.Dv > 256 || g.D < 8 || g.Dv < 8);
-	const bool use_anyd = anyd_ok && (anyd == 2 || !old_ok);
-	// few query rows against a long cache: sdpa_decode_f16_kernel (sdpa_decode_f16.h) in front of both (key SDPA_F16_DECODE: 0 = never, n = from n keys on)
-	const long decode = tune(TUNE_SDPA_F16_DECODE);
-	const bool use_decode = decode > 0 && (long)g.R * g.ratio <= SDPA_DECODE_ROWS && g.C >= decode && !(g.D % 8 || g.Dv % 8 || g.D > 256 || g.Dv > 256 || g.D < 8 || g.Dv < 8);
-	if (!old_ok && !use_anyd && !use_decode) return CCV_NNC_EXEC_NO_KERNEL;
+	const int family = sdpa_route_half(g, bhd_chunks(qi, 16, 2) && bhd_chunks(ki, 16, 2) && bhd_chunks(vi, 16, 2) && bhd_chunks(ci, 8, 2), true).forw;
+	if (family == SDPA_NONE) return CCV_NNC_EXEC_NO_KERNEL;
 	if (w && !sdpa_projection_ok(g, c, outputs[0], w, bias)) return CCV_NNC_EXEC_NO_KERNEL; // (the fp32 route answers)
-	if ((((uintptr_t)q->data.u8 | (uintptr_t)k->data.u8 | (uintptr_t)v->data.u8) & 15) || ((uintptr_t)c->data.u8 & 7)) return CCV_NNC_EXEC_NO_KERNEL;
-	if ((g.q_sb | g.q_sr | g.q_sh | g.k_sb | g.k_sc | g.k_sh | g.v_sb | g.v_sc | g.v_sh) & 7) return CCV_NNC_EXEC_NO_KERNEL;
-	if ((g.o_sb | g.o_sr | g.o_sh) & 3) return CCV_NNC_EXEC_NO_KERNEL;
 	float* lse = 0;
 	if (lse_t) {
 		if (CCV_GET_DATA_TYPE(lse_t->info.datatype) != CCV_32F || !tensor_contiguous(lse_t) || tensor_count(lse_t->info) != (size_t)g.B * g.Hq * g.R) return CCV_NNC_EXEC_NO_KERNEL;
@@ -1099,11 +1142,11 @@ static int sdpa_forw_half(EXEC_ARGS)
 	}
 	MarkerScope marker(cmd.cmd);
 	if (!g.R || !g.Hq || !g.B) return CCV_NNC_EXEC_SUCCESS;
-	if (use_decode) {
-		const int r = sdpa_decode_f16_run(g, (const half_t*)q->data.u8, (const half_t*)k->data.u8, (const half_t*)v->data.u8, mask ? (const half_t*)mask->data.u8 : 0, (half_t*)c->data.u8, lse, stream_context);
+	const half_t* const mp = mask ? (const half_t*)mask->data.u8 : 0;
+	if (family == SDPA_DECODE) {
+		const int r = sdpa_decode_f16_run(g, (const half_t*)qi.p, (const half_t*)ki.p, (const half_t*)vi.p, mp, (half_t*)ci.p, lse, stream_context);
 		if (r != CCV_NNC_EXEC_SUCCESS) return r;
-	} else
-	(use_anyd ? sdpa_fwd_anyd_f16_launch : sdpa_forw_f16_launch)(g, (const half_t*)q->data.u8, (const half_t*)k->data.u8, (const half_t*)v->data.u8, mask ? (const half_t*)mask->data.u8 : 0, (half_t*)c->data.u8, lse, stream_of(stream_context));
+	} else (family == SDPA_ANYD ? sdpa_fwd_anyd_f16_launch : sdpa_forw_f16_launch)(g, (const half_t*)qi.p, (const half_t*)ki.p, (const half_t*)vi.p, mp, (half_t*)ci.p, lse, stream_of(stream_context));
 	if (!w) return CCV_NNC_EXEC_SUCCESS;
 	return sdpa_projection(g, c, outputs[0], w, bias, stream_context); // a GEMM_FORWARD on the half tensors: the f16 contraction core
 }
@@ -1125,16 +1168,11 @@ static int _sdpa_back(EXEC_ARGS)
 	if (input_size < 6 || output_size < 3 || !inputs[0] || !inputs[3] || !inputs[4] || !inputs[5]) return CCV_NNC_EXEC_INVALID;
 	const ccv_nnc_tensor_t* mask = input_size > 6 ? inputs[6] : 0;
 	if (input_size > 7 && inputs[7]) return CCV_NNC_EXEC_INVALID; // the head-unifying projection has no backward here (nor in the backend replaced, flash_attn.cu:246-248)
-	ccv_nnc_tensor_t* const dq = outputs[0];
-	ccv_nnc_tensor_t* const dk = outputs[1];
-	ccv_nnc_tensor_t* const dv = outputs[2];
 	sdpa_geom_t g;
-	bhd_t qi, ki, vi, gi, dqi, dki, dvi;
-	if (!sdpa_geometry(cmd, inputs[3], inputs[4], inputs[5], mask, &g, &qi, &ki, &vi) || !bhd(inputs[0], &gi)) return CCV_NNC_EXEC_INVALID;
-	if (gi.b != g.B || gi.n != g.R || gi.h != g.Hq || gi.d != g.Dv) return CCV_NNC_EXEC_INVALID;
-	if (dq && (!bhd(dq, &dqi) || dqi.b != g.B || dqi.n != g.R || dqi.h != g.Hq || dqi.d != g.D)) return CCV_NNC_EXEC_INVALID;
-	if (dk && (!bhd(dk, &dki) || dki.b != g.B || dki.n != g.C || dki.h != g.Hk || dki.d != g.D)) return CCV_NNC_EXEC_INVALID;
-	if (dv && (!bhd(dv, &dvi) || dvi.b != g.B || dvi.n != g.C || dvi.h != g.Hk || dvi.d != g.Dv)) return CCV_NNC_EXEC_INVALID;
+	bhd_t qi, ki, vi;
+	sdpa_back_ops_t a;
+	if (sdpa_geometry(cmd, inputs[3], inputs[4], inputs[5], mask, CCV_32F, &g, &qi, &ki, &vi) || !bhd(inputs[0], &a.g, CCV_32F) || !bhd_is(a.g, g.B, g.R, g.Hq, g.Dv)) return CCV_NNC_EXEC_INVALID;
+	if (!sdpa_gradients(g, outputs, CCV_32F, &a)) return CCV_NNC_EXEC_INVALID;
 	if (!g.B || !g.R || !g.C) return CCV_NNC_EXEC_SUCCESS;
 	const size_t rows = (size_t)g.B * g.Hq * g.R;
 	const size_t o_bytes = (sizeof(float) * rows * g.Dv + 255) & ~(size_t)255, r_bytes = (sizeof(float) * rows + 255) & ~(size_t)255;
@@ -1142,109 +1180,61 @@ static int _sdpa_back(EXEC_ARGS)
 	if (!ws) return CCV_NNC_EXEC_OOM;
 	float* const o = (float*)ws; float* const lse = (float*)(ws + o_bytes); float* const delta = (float*)(ws + o_bytes + r_bytes);
 	hipStream_t stream = stream_of(stream_context);
-	sdpa_geom_t gf = g;
-	gf.o_sb = (long)g.R * g.Hq * g.Dv; gf.o_sr = (long)g.Hq * g.Dv; gf.o_sh = g.Dv;
-	const float* const qp = inputs[3]->data.f32; const float* const kp = inputs[4]->data.f32; const float* const vp = inputs[5]->data.f32;
-	const float* const mp = mask ? mask->data.f32 : 0; const float* const gp = inputs[0]->data.f32;
-	int ret = sdpa_forward_launch(gf, qp, kp, vp, mp, o, lse, stream);
+	a.q = qi.p; a.k = ki.p; a.v = vi.p; a.mask = mask ? mask->data.u8 : 0; a.lse = lse; a.delta = delta;
+	const sdpa_route_fp32_t route = sdpa_route_fp32(g, qi, ki, vi, &a.g);
+	int ret = sdpa_forward_launch(sdpa_rerun_geometry(g), route.forw, (const float*)a.q, (const float*)a.k, (const float*)a.v, (const float*)a.mask, o, lse, stream);
 	if (ret != CCV_NNC_EXEC_SUCCESS) return ret;
-	hipLaunchKernelGGL(sdpa_delta_kernel, dim3(grid_for(rows, 256)), dim3(256), 0, stream, g, gp, gi.sb, gi.sn, gi.sh, (const float*)o, delta);
+	hipLaunchKernelGGL(sdpa_delta_kernel, dim3(grid_for(rows, 256)), dim3(256), 0, stream, g, (const float*)a.g.p, a.g.sb, a.g.sn, a.g.sh, (const float*)o, delta);
 	HIP_ENFORCE(hipGetLastError());
+	const sdpa_ints<64, 128, 256> valu{}; // the VALU kernels' LDS layouts: the larger of D and Dv
 	const int dm = g.D > g.Dv ? g.D : g.Dv;
-	// the matrix-core kernels: whole 16-byte chunks of every row, whole 32-column output tiles
-	const bool rows16 = !(((uintptr_t)qp | (uintptr_t)kp | (uintptr_t)vp | (uintptr_t)gp) & 15) && !((g.q_sb | g.q_sr | g.q_sh | g.k_sb | g.k_sc | g.k_sh | g.v_sb | g.v_sc | g.v_sh | gi.sb | gi.sn | gi.sh) & 3);
-	const bool mfma_dq = tune(TUNE_SDPA_MFMA) && rows16 && g.D % 32 == 0 && g.Dv % 8 == 0 && g.D <= 128 && g.Dv <= 128;
-	const bool mfma_dkv = tune(TUNE_SDPA_MFMA) && rows16 && g.D % 32 == 0 && g.Dv % 32 == 0 && g.D <= 128 && g.Dv <= 128;
-	if (dq && mfma_dq) {
+	if (a.dq.p && route.dq) {
 		const dim3 grid((g.R + 127) / 128, g.Hq, g.B);
-		const int td = g.D / 32;
 		note_kernel("sdpa_dq_mfma");
 		ProfScope prof("sdpa_dq|nnc::sdpa_dq_mfma_kernel", 2.0 * g.B * g.Hq * (double)g.R * g.C * (2 * g.D + g.Dv), 0, g.R, g.C, g.D, g.B * g.Hq, 1, stream);
-#define SDPA_DQ(DH, GH, TD) hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_dq_mfma_kernel<DH, GH, TD>), grid, dim3(256), 0, stream, g, qp, kp, vp, mp, gp, gi.sb, gi.sn, gi.sh, (const float*)lse, (const float*)delta, dq->data.f32, dqi.sb, dqi.sn, dqi.sh)
-		if (g.Dv <= 64) { if (td == 1) SDPA_DQ(32, 32, 1); else if (td == 2) SDPA_DQ(32, 32, 2); else if (td == 3) SDPA_DQ(64, 32, 3); else SDPA_DQ(64, 32, 4); }
-		else { if (td == 1) SDPA_DQ(32, 64, 1); else if (td == 2) SDPA_DQ(32, 64, 2); else if (td == 3) SDPA_DQ(64, 64, 3); else SDPA_DQ(64, 64, 4); }
-#undef SDPA_DQ
+		sdpa_pick(sdpa_ints<32, 64>(), g.Dv / 2, sdpa_ints<1, 2, 3, 4>(), g.D / 32, [&](auto gh, auto td) { // Dv / 2 rounded up to 32 or 64, D / 32; D / 2 likewise
+			sdpa_launch_dq<float>(sdpa_dq_mfma_kernel<(decltype(td)::value <= 2 ? 32 : 64), decltype(gh)::value, decltype(td)::value>, grid, stream, g, a); });
 		HIP_ENFORCE(hipGetLastError());
-	} else if (dq) {
-		const dim3 grid((g.R + BR - 1) / BR, g.Hq, g.B);
-		if (dm <= 64) hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_dq_kernel<64, 64>), grid, dim3(256), 0, stream, g, qp, kp, vp, mp, gp, gi.sb, gi.sn, gi.sh, (const float*)lse, (const float*)delta, dq->data.f32, dqi.sb, dqi.sn, dqi.sh);
-		else if (dm <= 128) hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_dq_kernel<128, 32>), grid, dim3(256), 0, stream, g, qp, kp, vp, mp, gp, gi.sb, gi.sn, gi.sh, (const float*)lse, (const float*)delta, dq->data.f32, dqi.sb, dqi.sn, dqi.sh);
-		else hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_dq_kernel<256, 16>), grid, dim3(256), 0, stream, g, qp, kp, vp, mp, gp, gi.sb, gi.sn, gi.sh, (const float*)lse, (const float*)delta, dq->data.f32, dqi.sb, dqi.sn, dqi.sh);
+	} else if (a.dq.p) {
+		sdpa_pick(valu, dm, [&](auto dmax) { sdpa_launch_dq<float>(sdpa_dq_kernel<decltype(dmax)::value, 4096 / decltype(dmax)::value>, dim3((g.R + BR - 1) / BR, g.Hq, g.B), stream, g, a); });
 		HIP_ENFORCE(hipGetLastError());
 	}
-	if ((dk || dv) && mfma_dkv) {
+	if ((a.dk.p || a.dv.p) && route.dkv) {
 		const dim3 grid((g.C + 127) / 128, g.Hk, g.B);
-		float* const dkp = dk ? dk->data.f32 : 0; float* const dvp = dv ? dv->data.f32 : 0;
-		const long ksb = dk ? dki.sb : 0, ksn = dk ? dki.sn : 0, ksh = dk ? dki.sh : 0, vsb = dv ? dvi.sb : 0, vsn = dv ? dvi.sn : 0, vsh = dv ? dvi.sh : 0;
 		note_kernel("sdpa_dkv_mfma");
 		ProfScope prof("sdpa_dkv|nnc::sdpa_dkv_mfma_kernel", 2.0 * g.B * g.Hq * (double)g.R * g.C * (2 * g.D + 2 * g.Dv), 0, g.C, g.R, g.D, g.B * g.Hk, 1, stream);
-#define SDPA_DKV(TD, TV) hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_dkv_mfma_kernel<TD, TV>), grid, dim3(256), 0, stream, g, qp, kp, vp, mp, gp, gi.sb, gi.sn, gi.sh, (const float*)lse, (const float*)delta, dkp, ksb, ksn, ksh, dvp, vsb, vsn, vsh)
-		if (g.D <= 64 && g.Dv <= 64) {
-			if (g.D == 32) { if (g.Dv == 32) SDPA_DKV(1, 1); else SDPA_DKV(1, 2); }
-			else { if (g.Dv == 32) SDPA_DKV(2, 1); else SDPA_DKV(2, 2); }
-		} else {
-			// one gradient per pass (registers): dv first, then dk
-#define SDPA_DKV2(TD, TV) do { if (dvp) hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_dkv_mfma_kernel<TD, TV, false, true>), grid, dim3(256), 0, stream, g, qp, kp, vp, mp, gp, gi.sb, gi.sn, gi.sh, (const float*)lse, (const float*)delta, dkp, ksb, ksn, ksh, dvp, vsb, vsn, vsh); \
-			if (dkp) hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_dkv_mfma_kernel<TD, TV, true, false>), grid, dim3(256), 0, stream, g, qp, kp, vp, mp, gp, gi.sb, gi.sn, gi.sh, (const float*)lse, (const float*)delta, dkp, ksb, ksn, ksh, dvp, vsb, vsn, vsh); } while (0)
-#define SDPA_DKV2_TV(TD) do { switch (g.Dv / 32) { case 1: SDPA_DKV2(TD, 1); break; case 2: SDPA_DKV2(TD, 2); break; case 3: SDPA_DKV2(TD, 3); break; default: SDPA_DKV2(TD, 4); break; } } while (0)
-			switch (g.D / 32) { case 1: SDPA_DKV2_TV(1); break; case 2: SDPA_DKV2_TV(2); break; case 3: SDPA_DKV2_TV(3); break; default: SDPA_DKV2_TV(4); break; }
-#undef SDPA_DKV2_TV
-#undef SDPA_DKV2
-		}
-#undef SDPA_DKV
+		const sdpa_ints<1, 2, 3, 4> tiles{}; // D / 32, Dv / 32
+		if (g.D <= 64 && g.Dv <= 64) sdpa_pick(sdpa_ints<1, 2>(), g.D / 32, sdpa_ints<1, 2>(), g.Dv / 32, [&](auto td, auto tv) { // both gradients in one pass
+			sdpa_launch_dkv<float>(sdpa_dkv_mfma_kernel<decltype(td)::value, decltype(tv)::value>, grid, stream, g, a); });
+		else sdpa_pick(tiles, g.D / 32, tiles, g.Dv / 32, [&](auto td, auto tv) { // one gradient per pass (registers): dv first, then dk
+			if (a.dv.p) sdpa_launch_dkv<float>(sdpa_dkv_mfma_kernel<decltype(td)::value, decltype(tv)::value, false, true>, grid, stream, g, a);
+			if (a.dk.p) sdpa_launch_dkv<float>(sdpa_dkv_mfma_kernel<decltype(td)::value, decltype(tv)::value, true, false>, grid, stream, g, a); });
 		HIP_ENFORCE(hipGetLastError());
-	} else if (dk || dv) {
-		const dim3 grid((g.C + BR - 1) / BR, g.Hk, g.B);
-		float* const dkp = dk ? dk->data.f32 : 0; float* const dvp = dv ? dv->data.f32 : 0;
-		const long ksb = dk ? dki.sb : 0, ksn = dk ? dki.sn : 0, ksh = dk ? dki.sh : 0, vsb = dv ? dvi.sb : 0, vsn = dv ? dvi.sn : 0, vsh = dv ? dvi.sh : 0;
-		if (dm <= 64) hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_dkv_kernel<64>), grid, dim3(256), 0, stream, g, qp, kp, vp, mp, gp, gi.sb, gi.sn, gi.sh, (const float*)lse, (const float*)delta, dkp, ksb, ksn, ksh, dvp, vsb, vsn, vsh);
-		else if (dm <= 128) hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_dkv_kernel<128>), grid, dim3(256), 0, stream, g, qp, kp, vp, mp, gp, gi.sb, gi.sn, gi.sh, (const float*)lse, (const float*)delta, dkp, ksb, ksn, ksh, dvp, vsb, vsn, vsh);
-		else hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_dkv_kernel<256>), grid, dim3(256), 0, stream, g, qp, kp, vp, mp, gp, gi.sb, gi.sn, gi.sh, (const float*)lse, (const float*)delta, dkp, ksb, ksn, ksh, dvp, vsb, vsn, vsh);
+	} else if (a.dk.p || a.dv.p) {
+		sdpa_pick(valu, dm, [&](auto dmax) { sdpa_launch_dkv<float>(sdpa_dkv_kernel<decltype(dmax)::value>, dim3((g.C + BR - 1) / BR, g.Hk, g.B), stream, g, a); });
 		HIP_ENFORCE(hipGetLastError());
 	}
 	return CCV_NNC_EXEC_SUCCESS;
 }
 
-// CCV_16F g / q / k / v -> dq / dk / dv: sdpa_dq_f16_kernel / sdpa_dkv_f16_kernel where their conditions hold, the kernels of sdpa_anyd_f16_back.h for the other
-// head sizes in 8s up to 256 (CCV_NNC_EXEC_NO_KERNEL = not this path)
+// CCV_16F g / q / k / v -> dq / dk / dv: the backward family of sdpa_route_half behind the forward re-run on its forward family, the decode kernel excluded
+// (CCV_NNC_EXEC_NO_KERNEL = not this path)
 static int sdpa_back_half(EXEC_ARGS)
 {
 	if (input_size < 6 || output_size < 3 || !inputs[0] || !inputs[3] || !inputs[4] || !inputs[5]) return CCV_NNC_EXEC_NO_KERNEL;
 	for (int i = 7; i < input_size && i < 9; i++) if (inputs[i]) return CCV_NNC_EXEC_NO_KERNEL; // the head projection: the fp32 route
 	const ccv_nnc_tensor_t* const mask = input_size > 6 ? inputs[6] : 0;
 	if (!tune(TUNE_SDPA_MFMA)) return CCV_NNC_EXEC_NO_KERNEL;
-	ccv_nnc_tensor_t* const dq = outputs[0]; ccv_nnc_tensor_t* const dk = outputs[1]; ccv_nnc_tensor_t* const dv = outputs[2];
-	const ccv_nnc_tensor_t* const q = inputs[3]; const ccv_nnc_tensor_t* const k = inputs[4]; const ccv_nnc_tensor_t* const v = inputs[5];
-	bhd_t qi, ki, vi, gi, dqi, dki, dvi;
-	if (!bhd(q, &qi, CCV_16F) || !bhd(k, &ki, CCV_16F) || !bhd(v, &vi, CCV_16F) || !bhd(inputs[0], &gi, CCV_16F)) return CCV_NNC_EXEC_NO_KERNEL;
-	if (tensor_nd(q->info.dim) != tensor_nd(k->info.dim) || tensor_nd(k->info.dim) != tensor_nd(v->info.dim)) return CCV_NNC_EXEC_NO_KERNEL;
-	if (qi.b != ki.b || ki.b != vi.b || qi.d != ki.d || ki.n != vi.n || ki.h != vi.h || qi.h < ki.h || qi.h % ki.h) return CCV_NNC_EXEC_NO_KERNEL;
 	sdpa_geom_t g;
-	memset(&g, 0, sizeof(g));
-	g.B = qi.b; g.R = qi.n; g.C = ki.n; g.Hq = qi.h; g.Hk = ki.h; g.D = qi.d; g.Dv = vi.d; g.ratio = qi.h / ki.h;
-	g.q_sb = qi.sb; g.q_sr = qi.sn; g.q_sh = qi.sh; g.k_sb = ki.sb; g.k_sc = ki.sn; g.k_sh = ki.sh; g.v_sb = vi.sb; g.v_sc = vi.sn; g.v_sh = vi.sh;
-	g.scale = cmd.info.scaled_dot_product_attention.scale;
-	g.causal = cmd.info.scaled_dot_product_attention.is_causal;
-	if (gi.b != g.B || gi.n != g.R || gi.h != g.Hq || gi.d != g.Dv) return CCV_NNC_EXEC_INVALID;
-	if (dq && (!bhd(dq, &dqi, CCV_16F) || dqi.b != g.B || dqi.n != g.R || dqi.h != g.Hq || dqi.d != g.D)) return CCV_NNC_EXEC_NO_KERNEL;
-	if (dk && (!bhd(dk, &dki, CCV_16F) || dki.b != g.B || dki.n != g.C || dki.h != g.Hk || dki.d != g.D)) return CCV_NNC_EXEC_NO_KERNEL;
-	if (dv && (!bhd(dv, &dvi, CCV_16F) || dvi.b != g.B || dvi.n != g.C || dvi.h != g.Hk || dvi.d != g.Dv)) return CCV_NNC_EXEC_NO_KERNEL;
-	// sdpa_dq_f16_kernel / sdpa_dkv_f16_kernel keep the shapes they take; the kernels of sdpa_anyd_f16_back.h take the others in 8s up to 256 (key SDPA_F16_ANYD:
-	// 0 = never, 2 = every shape they can, for measurements); the forward re-run is the kernel sdpa_forw_half picks for the shape
-	const long anyd = tune(TUNE_SDPA_F16_ANYD);
-	const bool old_ok = !(g.D % 32 || g.Dv % 32 || g.D > 128 || g.Dv > 128);
-	const bool anyd_ok = anyd && !(g.D % 8 || g.Dv % 8 || g.D > 256 || g.Dv > 256 || g.D < 8 || g.Dv < 8);
-	const bool use_anyd = anyd_ok && (anyd == 2 || !old_ok);
-	if (!old_ok && !use_anyd) return CCV_NNC_EXEC_NO_KERNEL;
-	const bool forw_old_ok = !(g.D % 16 || g.Dv % 32 || g.D > 128 || g.Dv > 128 || g.D < 16);
-	const bool forw_anyd = anyd_ok && (anyd == 2 || !forw_old_ok);
-	if (mask && !sdpa_mask_geometry(mask, &g, CCV_16F)) return CCV_NNC_EXEC_NO_KERNEL;
-	const half_t* const mp = mask ? (const half_t*)mask->data.u8 : 0;
-	if (((uintptr_t)q->data.u8 | (uintptr_t)k->data.u8 | (uintptr_t)v->data.u8 | (uintptr_t)inputs[0]->data.u8) & 15) return CCV_NNC_EXEC_NO_KERNEL;
-	if ((g.q_sb | g.q_sr | g.q_sh | g.k_sb | g.k_sc | g.k_sh | g.v_sb | g.v_sc | g.v_sh | gi.sb | gi.sn | gi.sh) & 7) return CCV_NNC_EXEC_NO_KERNEL;
-	if (dq && ((((uintptr_t)dq->data.u8) & 7) || ((dqi.sb | dqi.sn | dqi.sh) & 3))) return CCV_NNC_EXEC_NO_KERNEL;
-	if (dk && ((((uintptr_t)dk->data.u8) & 7) || ((dki.sb | dki.sn | dki.sh) & 3))) return CCV_NNC_EXEC_NO_KERNEL;
-	if (dv && ((((uintptr_t)dv->data.u8) & 7) || ((dvi.sb | dvi.sn | dvi.sh) & 3))) return CCV_NNC_EXEC_NO_KERNEL;
+	bhd_t qi, ki, vi;
+	sdpa_back_ops_t a;
+	const int parsed = sdpa_geometry(cmd, inputs[3], inputs[4], inputs[5], mask, CCV_16F, &g, &qi, &ki, &vi);
+	if (parsed == SDPA_NO_QKV || !bhd(inputs[0], &a.g, CCV_16F)) return CCV_NNC_EXEC_NO_KERNEL;
+	if (!bhd_is(a.g, g.B, g.R, g.Hq, g.Dv)) return CCV_NNC_EXEC_INVALID; // (in front of every other refusal)
+	if (parsed != SDPA_PARSED || !sdpa_gradients(g, outputs, CCV_16F, &a)) return CCV_NNC_EXEC_NO_KERNEL;
+	const bool chunks = bhd_chunks(qi, 16, 2) && bhd_chunks(ki, 16, 2) && bhd_chunks(vi, 16, 2) && bhd_chunks(a.g, 16, 2) && bhd_chunks(a.dq, 8, 2) && bhd_chunks(a.dk, 8, 2) && bhd_chunks(a.dv, 8, 2);
+	const sdpa_route_t route = sdpa_route_half(g, chunks, false);
+	if (route.back == SDPA_NONE) return CCV_NNC_EXEC_NO_KERNEL;
 	MarkerScope marker(cmd.cmd);
 	if (!g.B || !g.R || !g.C) return CCV_NNC_EXEC_SUCCESS;
 	const size_t rows = (size_t)g.B * g.Hq * g.R;
@@ -1253,39 +1243,27 @@ static int sdpa_back_half(EXEC_ARGS)
 	if (!ws) return CCV_NNC_EXEC_OOM;
 	half_t* const o = (half_t*)ws; float* const lse = (float*)(ws + o_bytes); float* const delta = (float*)(ws + o_bytes + r_bytes);
 	hipStream_t stream = stream_of(stream_context);
-	sdpa_geom_t gf = g;
-	gf.o_sb = (long)g.R * g.Hq * g.Dv; gf.o_sr = (long)g.Hq * g.Dv; gf.o_sh = g.Dv;
-	const half_t* const qp = (const half_t*)q->data.u8; const half_t* const kp = (const half_t*)k->data.u8; const half_t* const vp = (const half_t*)v->data.u8; const half_t* const gp = (const half_t*)inputs[0]->data.u8;
-	(forw_anyd ? sdpa_fwd_anyd_f16_launch : sdpa_forw_f16_launch)(gf, qp, kp, vp, mp, o, lse, stream);
-	hipLaunchKernelGGL(sdpa_delta_h_kernel, dim3(grid_for(rows, 256)), dim3(256), 0, stream, g, gp, gi.sb, gi.sn, gi.sh, (const half_t*)o, delta);
+	a.q = qi.p; a.k = ki.p; a.v = vi.p; a.mask = mask ? mask->data.u8 : 0; a.lse = lse; a.delta = delta;
+	(route.forw == SDPA_ANYD ? sdpa_fwd_anyd_f16_launch : sdpa_forw_f16_launch)(sdpa_rerun_geometry(g), (const half_t*)a.q, (const half_t*)a.k, (const half_t*)a.v, (const half_t*)a.mask, o, lse, stream);
+	hipLaunchKernelGGL(sdpa_delta_h_kernel, dim3(grid_for(rows, 256)), dim3(256), 0, stream, g, (const half_t*)a.g.p, a.g.sb, a.g.sn, a.g.sh, (const half_t*)o, delta);
 	HIP_ENFORCE(hipGetLastError());
-	if (use_anyd) {
-		sdpa_bwd_anyd_f16_launch(g, qp, kp, vp, mp, gp, gi.sb, gi.sn, gi.sh, (const float*)lse, (const float*)delta, dq ? (half_t*)dq->data.u8 : 0, dq ? dqi.sb : 0, dq ? dqi.sn : 0, dq ? dqi.sh : 0,
-			dk ? (half_t*)dk->data.u8 : 0, dk ? dki.sb : 0, dk ? dki.sn : 0, dk ? dki.sh : 0, dv ? (half_t*)dv->data.u8 : 0, dv ? dvi.sb : 0, dv ? dvi.sn : 0, dv ? dvi.sh : 0, stream);
+	if (route.back == SDPA_ANYD) {
+		sdpa_bwd_anyd_f16_launch(g, a, stream);
 		return CCV_NNC_EXEC_SUCCESS;
 	}
-#define SDPA_BY_GS(KERNEL, DS, ...) do { switch (g.Dv / 32) { \
-		case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<DS, 2>), __VA_ARGS__); break; case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<DS, 4>), __VA_ARGS__); break; \
-		case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<DS, 6>), __VA_ARGS__); break; default: hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<DS, 8>), __VA_ARGS__); break; } } while (0)
-#define SDPA_BY_DS(KERNEL, ...) do { switch (g.D / 32) { \
-		case 1: SDPA_BY_GS(KERNEL, 2, __VA_ARGS__); break; case 2: SDPA_BY_GS(KERNEL, 4, __VA_ARGS__); break; \
-		case 3: SDPA_BY_GS(KERNEL, 6, __VA_ARGS__); break; default: SDPA_BY_GS(KERNEL, 8, __VA_ARGS__); break; } } while (0)
-	if (dq) {
+	const sdpa_ints<2, 4, 6, 8> in32s{}; // D / 16 and Dv / 16, both even
+	if (a.dq.p) {
 		note_kernel("sdpa_dq_f16");
 		ProfScope prof("sdpa_dq_h|nnc::sdpa_dq_f16_kernel", 2.0 * g.B * g.Hq * (double)g.R * g.C * (2 * g.D + g.Dv), 0, g.R, g.C, g.D, g.B * g.Hq, 1, stream);
-		SDPA_BY_DS(sdpa_dq_f16_kernel, dim3((g.R + 127) / 128, g.Hq, g.B), dim3(256), 0, stream, g, qp, kp, vp, mp, gp, gi.sb, gi.sn, gi.sh, (const float*)lse, (const float*)delta, (half_t*)dq->data.u8, dqi.sb, dqi.sn, dqi.sh);
+		sdpa_pick(in32s, g.D / 16, in32s, g.Dv / 16, [&](auto ds, auto gs) { sdpa_launch_dq<half_t>(sdpa_dq_f16_kernel<decltype(ds)::value, decltype(gs)::value>, dim3((g.R + 127) / 128, g.Hq, g.B), stream, g, a); });
 		HIP_ENFORCE(hipGetLastError());
 	}
-	if (dk || dv) {
-		half_t* const dkp = dk ? (half_t*)dk->data.u8 : 0; half_t* const dvp = dv ? (half_t*)dv->data.u8 : 0;
-		const long ksb = dk ? dki.sb : 0, ksn = dk ? dki.sn : 0, ksh = dk ? dki.sh : 0, vsb = dv ? dvi.sb : 0, vsn = dv ? dvi.sn : 0, vsh = dv ? dvi.sh : 0;
+	if (a.dk.p || a.dv.p) {
 		note_kernel("sdpa_dkv_f16");
 		ProfScope prof("sdpa_dkv_h|nnc::sdpa_dkv_f16_kernel", 2.0 * g.B * g.Hq * (double)g.R * g.C * (2 * g.D + 2 * g.Dv), 0, g.C, g.R, g.D, g.B * g.Hk, 1, stream);
-		SDPA_BY_DS(sdpa_dkv_f16_kernel, dim3((g.C + 127) / 128, g.Hk, g.B), dim3(256), 0, stream, g, qp, kp, vp, mp, gp, gi.sb, gi.sn, gi.sh, (const float*)lse, (const float*)delta, dkp, ksb, ksn, ksh, dvp, vsb, vsn, vsh);
+		sdpa_pick(in32s, g.D / 16, in32s, g.Dv / 16, [&](auto ds, auto gs) { sdpa_launch_dkv<half_t>(sdpa_dkv_f16_kernel<decltype(ds)::value, decltype(gs)::value>, dim3((g.C + 127) / 128, g.Hk, g.B), stream, g, a); });
 		HIP_ENFORCE(hipGetLastError());
 	}
-#undef SDPA_BY_DS
-#undef SDPA_BY_GS
 	return CCV_NNC_EXEC_SUCCESS;
 }
 static int _sdpa_back_any(EXEC_ARGS)

@@ -24,6 +24,22 @@
 #pragma once
 
 template <int TV> constexpr int sdpa_anyd_vpitch() { return 32 * TV + (TV % 2 ? 0 : 32); }
+// the instances of this file's kernel and of sdpa_anyd_f16_back.h's: 16-term steps over D in 2s, 32-column tiles of Dv
+using sdpa_anyd_ds = sdpa_ints<2, 4, 6, 8, 10, 12, 14, 16>;
+using sdpa_anyd_tv = sdpa_ints<1, 2, 3, 4, 6, 8>;
+// The lane's chunks of the key block at y, into its registers kr[NK] / vr[NV] (this file's kernel and the dq kernel of sdpa_anyd_f16_back.h: K tile rows of KCH
+// chunks off kbase, V tile rows of VCH chunks off vbase): chunk c = t + 256 jj is key c / KCH (c / VCH), halves 8 (c % KCH) .. + 7; past C, past D / Dv: zeros
+#define SDPA_ANYD_FETCH(y) do { \
+		_Pragma("unroll") for (int jj = 0; jj < NK; jj++) { \
+			const int c = t + 256 * jj, j = c / KCH, d = (c - j * KCH) << 3; \
+			kr[jj] = zero8; \
+			if (c < 32 * KCH && (y) + j < g.C && d < g.D) kr[jj] = *(const halfx8*)(kbase + (long)((y) + j) * g.k_sc + d); \
+		} \
+		_Pragma("unroll") for (int jj = 0; jj < NV; jj++) { \
+			const int c = t + 256 * jj, j = c / VCH, d = (c - j * VCH) << 3; \
+			vr[jj] = zero8; \
+			if (c < 32 * VCH && (y) + j < g.C && d < g.Dv) vr[jj] = *(const halfx8*)(vbase + (long)((y) + j) * g.v_sc + d); \
+		} } while (0)
 
 template <int DS, int TV> // DS >= ceil(D / 16), TV >= ceil(Dv / 32): the LDS and register layout; the steps and tiles past D / Dv are skipped (wave-uniform)
 __global__ void __launch_bounds__(256) sdpa_fwd_anyd_f16_kernel(const sdpa_geom_t g, const half_t* __restrict__ q, const half_t* __restrict__ k, const half_t* __restrict__ v, const half_t* __restrict__ mask, half_t* __restrict__ o, float* __restrict__ lse)
@@ -65,18 +81,6 @@ __global__ void __launch_bounds__(256) sdpa_fwd_anyd_f16_kernel(const sdpa_geom_
 	const half_t* const kbase = k + b * g.k_sb + hk * g.k_sh;
 	const half_t* const vbase = v + b * g.v_sb + hk * g.v_sh;
 	halfx8 kr[NK], vr[NV];
-	// the lane's chunks of the key block at y: chunk c = t + 256 jj is key c / KCH (c / VCH), halves 8 (c % KCH) .. + 7; past C, past D / Dv: zeros
-#define SDPA_ANYD_FETCH(y) do { \
-		_Pragma("unroll") for (int jj = 0; jj < NK; jj++) { \
-			const int c = t + 256 * jj, j = c / KCH, d = (c - j * KCH) << 3; \
-			kr[jj] = zero8; \
-			if (c < 32 * KCH && (y) + j < g.C && d < g.D) kr[jj] = *(const halfx8*)(kbase + (long)((y) + j) * g.k_sc + d); \
-		} \
-		_Pragma("unroll") for (int jj = 0; jj < NV; jj++) { \
-			const int c = t + 256 * jj, j = c / VCH, d = (c - j * VCH) << 3; \
-			vr[jj] = zero8; \
-			if (c < 32 * VCH && (y) + j < g.C && d < g.Dv) vr[jj] = *(const halfx8*)(vbase + (long)((y) + j) * g.v_sc + d); \
-		} } while (0)
 	if (vis_wg > 0) SDPA_ANYD_FETCH(0);
 	for (int y0 = 0; y0 < vis_wg; y0 += 32) {
 		__syncthreads(); // every wave is done with the tiles of the block before
@@ -126,8 +130,8 @@ __global__ void __launch_bounds__(256) sdpa_fwd_anyd_f16_kernel(const sdpa_geom_
 #pragma unroll
 				for (int r = 0; r < 16; r++) acc[tv][r] *= alpha;
 #pragma unroll
-		for (int tt = 0; tt < 2; tt++) {
-			const halfx8 pf = halfx8{ (half_t)s[8 * tt], (half_t)s[8 * tt + 1], (half_t)s[8 * tt + 2], (half_t)s[8 * tt + 3], (half_t)s[8 * tt + 4], (half_t)s[8 * tt + 5], (half_t)s[8 * tt + 6], (half_t)s[8 * tt + 7] };
+		for (int tt = 0; tt < 2; tt++) { // (sdpa_anyd_f16_back.h's sdpa_bwd_tr_products written out: through the helper 40 instances of this kernel compile differently)
+			const halfx8 pf = sdpa_half8(s, tt);
 			const half_t* const blk = Vs + (16 * tt + 4 * lh) * VP + 16 * (li >> 4);
 #pragma unroll
 			for (int t0 = 0; t0 < TV; t0 += 4) { // four output tiles per wait: the transpose reads are asm, hipcc does not count them
@@ -148,7 +152,6 @@ __global__ void __launch_bounds__(256) sdpa_fwd_anyd_f16_kernel(const sdpa_geom_
 			}
 		}
 	}
-#undef SDPA_ANYD_FETCH
 	if (x < g.R) {
 		const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
 		half_t* const orow = o + b * g.o_sb + (long)x * g.o_sr + h * g.o_sh;
@@ -169,16 +172,7 @@ static void sdpa_fwd_anyd_f16_launch(const sdpa_geom_t& g, const half_t* const q
 	const dim3 grid((g.R + 127) / 128, g.Hq, g.B);
 	note_kernel("sdpa_fwd_anyd_f16");
 	ProfScope prof("sdpa_fwd_h_anyd|nnc::sdpa_fwd_anyd_f16_kernel", 2.0 * g.B * g.Hq * (double)g.R * g.C * (g.D + g.Dv), 0, g.R, g.C, g.D, g.B * g.Hq, 1, stream);
-	const int tv = (g.Dv + 31) / 32;
-#define SDPA_ANYD(DS, TV) hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_fwd_anyd_f16_kernel<DS, TV>), grid, dim3(256), 0, stream, g, qp, kp, vp, mp, op, lse)
-#define SDPA_ANYD_TV(DS) do { \
-		if (tv == 1) SDPA_ANYD(DS, 1); else if (tv == 2) SDPA_ANYD(DS, 2); else if (tv == 3) SDPA_ANYD(DS, 3); else if (tv == 4) SDPA_ANYD(DS, 4); \
-		else if (tv <= 6) SDPA_ANYD(DS, 6); else SDPA_ANYD(DS, 8); } while (0)
-	switch ((g.D + 31) / 32) {
-		case 1: SDPA_ANYD_TV(2); break; case 2: SDPA_ANYD_TV(4); break; case 3: SDPA_ANYD_TV(6); break; case 4: SDPA_ANYD_TV(8); break;
-		case 5: SDPA_ANYD_TV(10); break; case 6: SDPA_ANYD_TV(12); break; case 7: SDPA_ANYD_TV(14); break; default: SDPA_ANYD_TV(16); break;
-	}
-#undef SDPA_ANYD_TV
-#undef SDPA_ANYD
+	sdpa_pick(sdpa_anyd_ds(), (g.D + 15) / 16, sdpa_anyd_tv(), (g.Dv + 31) / 32, [&](auto ds, auto tv) {
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_fwd_anyd_f16_kernel<decltype(ds)::value, decltype(tv)::value>), grid, dim3(256), 0, stream, g, qp, kp, vp, mp, op, lse); });
 	HIP_ENFORCE(hipGetLastError());
 }

@@ -23,10 +23,6 @@
 //          needs k, S and G only.
 #pragma once
 
-__device__ __forceinline__ halfx8 sdpa_bwd_half8(const floatx16& v, const int t16)
-{
-	return halfx8{ (half_t)v[8 * t16], (half_t)v[8 * t16 + 1], (half_t)v[8 * t16 + 2], (half_t)v[8 * t16 + 3], (half_t)v[8 * t16 + 4], (half_t)v[8 * t16 + 5], (half_t)v[8 * t16 + 6], (half_t)v[8 * t16 + 7] };
-}
 // acc[i] += (tile^T) b for the output tiles i < n: A = columns 32 i + (l & 31) of the tile rows 16 tt + 4 lh + 0..3 and + 8 (blk = that row, column 16 (li >> 4)), four
 // tiles per wait: the transpose reads are asm, hipcc does not count them
 template <int T>
@@ -97,19 +93,7 @@ __global__ void __launch_bounds__(256) sdpa_bwd_anyd_dq_f16_kernel(const sdpa_ge
 	const half_t* const kbase = k + b * g.k_sb + hk * g.k_sh;
 	const half_t* const vbase = v + b * g.v_sb + hk * g.v_sh;
 	halfx8 kr[NK], vr[NV];
-	// the lane's chunks of the key block at y: chunk c = t + 256 jj is key c / KCH (c / VCH), halves 8 (c % KCH) .. + 7; past C, past D / Dv: zeros
-#define SDPA_BWD_DQ_FETCH(y) do { \
-		_Pragma("unroll") for (int jj = 0; jj < NK; jj++) { \
-			const int c = t + 256 * jj, j = c / KCH, d = (c - j * KCH) << 3; \
-			kr[jj] = zero8; \
-			if (c < 32 * KCH && (y) + j < g.C && d < g.D) kr[jj] = *(const halfx8*)(kbase + (long)((y) + j) * g.k_sc + d); \
-		} \
-		_Pragma("unroll") for (int jj = 0; jj < NV; jj++) { \
-			const int c = t + 256 * jj, j = c / VCH, d = (c - j * VCH) << 3; \
-			vr[jj] = zero8; \
-			if (c < 32 * VCH && (y) + j < g.C && d < g.Dv) vr[jj] = *(const halfx8*)(vbase + (long)((y) + j) * g.v_sc + d); \
-		} } while (0)
-	if (vis_wg > 0) SDPA_BWD_DQ_FETCH(0);
+	if (vis_wg > 0) SDPA_ANYD_FETCH(0); // (sdpa_anyd_f16.h)
 	for (int y0 = 0; y0 < vis_wg; y0 += 32) {
 		__syncthreads(); // every wave is done with the tiles of the block before
 #pragma unroll
@@ -123,7 +107,7 @@ __global__ void __launch_bounds__(256) sdpa_bwd_anyd_dq_f16_kernel(const sdpa_ge
 			if (c < 32 * VCH) *(halfx8*)(Vs + j * VP + d) = vr[jj];
 		}
 		__syncthreads();
-		if (y0 + 32 < vis_wg) SDPA_BWD_DQ_FETCH(y0 + 32); // in flight while this block is computed
+		if (y0 + 32 < vis_wg) SDPA_ANYD_FETCH(y0 + 32); // in flight while this block is computed
 		if (y0 >= vis_wave) continue; // none of the wave's rows sees a key of this block (the barriers above are passed by every wave all the same)
 		floatx16 s, dp;
 #pragma unroll
@@ -144,9 +128,9 @@ __global__ void __launch_bounds__(256) sdpa_bwd_anyd_dq_f16_kernel(const sdpa_ge
 		}
 #pragma unroll
 		for (int tt = 0; tt < 2; tt++)
-			sdpa_bwd_tr_products<TD>(acc, td_n, Ks + (16 * tt + 4 * lh) * KP + 16 * (li >> 4), KP, li, sdpa_bwd_half8(s, tt));
+			sdpa_bwd_tr_products<TD>(acc, td_n, Ks + (16 * tt + 4 * lh) * KP + 16 * (li >> 4), KP, li, sdpa_half8(s, tt));
 	}
-#undef SDPA_BWD_DQ_FETCH
+#undef SDPA_ANYD_FETCH
 	if (x < g.R) {
 		half_t* const orow = dq + b * dq_sb + (long)x * dq_sr + h * dq_sh;
 #pragma unroll
@@ -267,8 +251,8 @@ __global__ void __launch_bounds__(256) sdpa_bwd_anyd_dkv_f16_kernel(const sdpa_g
 		}
 #pragma unroll
 		for (int tt = 0; tt < 2; tt++) {
-			if (want_v) sdpa_bwd_tr_products<NAV>(av, tv_n, Gs + (16 * tt + 4 * lh) * GP + 16 * (li >> 4), GP, li, sdpa_bwd_half8(s, tt));
-			if (want_k) sdpa_bwd_tr_products<NAK>(ak, td_n, Qs + (16 * tt + 4 * lh) * QP + 16 * (li >> 4), QP, li, sdpa_bwd_half8(dp, tt));
+			if (want_v) sdpa_bwd_tr_products<NAV>(av, tv_n, Gs + (16 * tt + 4 * lh) * GP + 16 * (li >> 4), GP, li, sdpa_half8(s, tt));
+			if (want_k) sdpa_bwd_tr_products<NAK>(ak, td_n, Qs + (16 * tt + 4 * lh) * QP + 16 * (li >> 4), QP, li, sdpa_half8(dp, tt));
 		}
 	}
 #undef SDPA_BWD_DKV_FETCH
@@ -297,62 +281,40 @@ __global__ void __launch_bounds__(256) sdpa_bwd_anyd_dkv_f16_kernel(const sdpa_g
 
 // D % 8 == 0, Dv % 8 == 0, 8 <= D, Dv <= 256; 16-byte aligned q / k / v / g rows, 8-byte aligned dq / dk / dv rows (the caller checks); lse, delta: the forward
 // re-run's log-sum-exp and sdpa_delta_h_kernel's row sums
-static void sdpa_bwd_anyd_f16_launch(const sdpa_geom_t& g, const half_t* const qp, const half_t* const kp, const half_t* const vp, const half_t* const mp, const half_t* const gp, const long g_sb, const long g_sr, const long g_sh, const float* const lse, const float* const delta,
-	half_t* const dqp, const long dq_sb, const long dq_sr, const long dq_sh, half_t* const dkp, const long dk_sb, const long dk_sc, const long dk_sh, half_t* const dvp, const long dv_sb, const long dv_sc, const long dv_sh, hipStream_t stream)
+static void sdpa_bwd_anyd_f16_launch(const sdpa_geom_t& g, const sdpa_back_ops_t& a, hipStream_t stream)
 {
-	const int tv = (g.Dv + 31) / 32, td = (g.D + 31) / 32;
-#define SDPA_BWD_TV(M, DS) do { \
-		if (tv == 1) M(DS, 1); else if (tv == 2) M(DS, 2); else if (tv == 3) M(DS, 3); else if (tv == 4) M(DS, 4); else if (tv <= 6) M(DS, 6); else M(DS, 8); } while (0)
-#define SDPA_BWD_DS(M) do { switch (td) { \
-		case 1: SDPA_BWD_TV(M, 2); break; case 2: SDPA_BWD_TV(M, 4); break; case 3: SDPA_BWD_TV(M, 6); break; case 4: SDPA_BWD_TV(M, 8); break; \
-		case 5: SDPA_BWD_TV(M, 10); break; case 6: SDPA_BWD_TV(M, 12); break; case 7: SDPA_BWD_TV(M, 14); break; default: SDPA_BWD_TV(M, 16); break; } } while (0)
+	const int ds = (g.D + 15) / 16, tv = (g.Dv + 31) / 32;
+	half_t* const dqp = (half_t*)a.dq.p; half_t* const dkp = (half_t*)a.dk.p; half_t* const dvp = (half_t*)a.dv.p;
 	if (dqp) {
 		const dim3 grid((g.R + 127) / 128, g.Hq, g.B);
 		note_kernel("sdpa_bwd_anyd_dq_f16");
 		ProfScope prof("sdpa_bwd_dq_h_anyd|nnc::sdpa_bwd_anyd_dq_f16_kernel", 2.0 * g.B * g.Hq * (double)g.R * g.C * (2 * g.D + g.Dv), 0, g.R, g.C, g.D, g.B * g.Hq, 1, stream);
-#define SDPA_BWD_DQ(DS, TV) hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_bwd_anyd_dq_f16_kernel<DS, TV>), grid, dim3(256), 0, stream, g, qp, kp, vp, mp, gp, g_sb, g_sr, g_sh, lse, delta, dqp, dq_sb, dq_sr, dq_sh)
-		SDPA_BWD_DS(SDPA_BWD_DQ);
-#undef SDPA_BWD_DQ
+		sdpa_pick(sdpa_anyd_ds(), ds, sdpa_anyd_tv(), tv, [&](auto s, auto t) { sdpa_launch_dq<half_t>(sdpa_bwd_anyd_dq_f16_kernel<decltype(s)::value, decltype(t)::value>, grid, stream, g, a); });
 		HIP_ENFORCE(hipGetLastError());
 	}
 	if (dkp || dvp) {
 		const dim3 grid((g.C + 127) / 128, g.Hk, g.B);
-#define SDPA_BWD_DKV_ARGS grid, dim3(256), 0, stream, g, qp, kp, vp, mp, gp, g_sb, g_sr, g_sh, lse, delta, dkp, dk_sb, dk_sc, dk_sh, dvp, dv_sb, dv_sc, dv_sh
 		note_kernel("sdpa_bwd_anyd_dkv_f16");
-		if (td <= 6 && tv <= 6) { // both gradients in one pass
+		if (ds <= 12 && tv <= 6) { // both gradients in one pass
 			ProfScope prof("sdpa_bwd_dkv_h_anyd|nnc::sdpa_bwd_anyd_dkv_f16_kernel", 2.0 * g.B * g.Hq * (double)g.R * g.C * ((dkp ? 2 * g.D + g.Dv : g.D) + (dvp ? g.Dv : 0)), 0, g.C, g.R, g.D, g.B * g.Hk, 1, stream);
-			switch (td) {
-#define SDPA_BWD_DKV(DS, TV) hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_bwd_anyd_dkv_f16_kernel<DS, TV, true, true>), SDPA_BWD_DKV_ARGS)
-#define SDPA_BWD_DKV_TV(DS) do { \
-		if (tv == 1) SDPA_BWD_DKV(DS, 1); else if (tv == 2) SDPA_BWD_DKV(DS, 2); else if (tv == 3) SDPA_BWD_DKV(DS, 3); else if (tv == 4) SDPA_BWD_DKV(DS, 4); else SDPA_BWD_DKV(DS, 6); } while (0)
-				case 1: SDPA_BWD_DKV_TV(2); break; case 2: SDPA_BWD_DKV_TV(4); break; case 3: SDPA_BWD_DKV_TV(6); break;
-				case 4: SDPA_BWD_DKV_TV(8); break; case 5: SDPA_BWD_DKV_TV(10); break; default: SDPA_BWD_DKV_TV(12); break;
-#undef SDPA_BWD_DKV_TV
-#undef SDPA_BWD_DKV
-			}
+			sdpa_pick(sdpa_ints<2, 4, 6, 8, 10, 12>(), ds, sdpa_ints<1, 2, 3, 4, 6>(), tv, [&](auto s, auto t) {
+				sdpa_launch_dkv<half_t>(sdpa_bwd_anyd_dkv_f16_kernel<decltype(s)::value, decltype(t)::value, true, true>, grid, stream, g, a); });
 			HIP_ENFORCE(hipGetLastError());
 		} else { // one gradient per pass (registers): dv first, then dk.  Only the instances this branch can reach are compiled: D > 192 with any Dv, or Dv > 192
-#define SDPA_BWD_SPLIT(M) do { \
-		if (td == 7) SDPA_BWD_TV(M, 14); else if (td == 8) SDPA_BWD_TV(M, 16); \
-		else switch (td) { case 1: M(2, 8); break; case 2: M(4, 8); break; case 3: M(6, 8); break; case 4: M(8, 8); break; case 5: M(10, 8); break; default: M(12, 8); break; } } while (0)
+			const auto pass = [&](auto do_k, auto do_v) {
+				constexpr bool DO_K = decltype(do_k)::value, DO_V = decltype(do_v)::value;
+				if (ds > 12) sdpa_pick(sdpa_ints<14, 16>(), ds, sdpa_anyd_tv(), tv, [&](auto s, auto t) { sdpa_launch_dkv<half_t>(sdpa_bwd_anyd_dkv_f16_kernel<decltype(s)::value, decltype(t)::value, DO_K, DO_V>, grid, stream, g, a); });
+				else sdpa_pick(sdpa_ints<2, 4, 6, 8, 10, 12>(), ds, [&](auto s) { sdpa_launch_dkv<half_t>(sdpa_bwd_anyd_dkv_f16_kernel<decltype(s)::value, 8, DO_K, DO_V>, grid, stream, g, a); });
+				HIP_ENFORCE(hipGetLastError());
+			};
 			if (dvp) {
 				ProfScope prof("sdpa_bwd_dv_h_anyd|nnc::sdpa_bwd_anyd_dkv_f16_kernel", 2.0 * g.B * g.Hq * (double)g.R * g.C * (g.D + g.Dv), 0, g.C, g.R, g.D, g.B * g.Hk, 1, stream);
-#define SDPA_BWD_DV(DS, TV) hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_bwd_anyd_dkv_f16_kernel<DS, TV, false, true>), SDPA_BWD_DKV_ARGS)
-				SDPA_BWD_SPLIT(SDPA_BWD_DV);
-#undef SDPA_BWD_DV
-				HIP_ENFORCE(hipGetLastError());
+				pass(std::false_type(), std::true_type());
 			}
 			if (dkp) {
 				ProfScope prof("sdpa_bwd_dk_h_anyd|nnc::sdpa_bwd_anyd_dkv_f16_kernel", 2.0 * g.B * g.Hq * (double)g.R * g.C * (2 * g.D + g.Dv), 0, g.C, g.R, g.D, g.B * g.Hk, 1, stream);
-#define SDPA_BWD_DK(DS, TV) hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_bwd_anyd_dkv_f16_kernel<DS, TV, true, false>), SDPA_BWD_DKV_ARGS)
-				SDPA_BWD_SPLIT(SDPA_BWD_DK);
-#undef SDPA_BWD_DK
-				HIP_ENFORCE(hipGetLastError());
+				pass(std::true_type(), std::false_type());
 			}
-#undef SDPA_BWD_SPLIT
 		}
-#undef SDPA_BWD_DKV_ARGS
 	}
-#undef SDPA_BWD_DS
-#undef SDPA_BWD_TV
 }

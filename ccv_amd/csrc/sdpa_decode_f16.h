@@ -152,7 +152,7 @@ __global__ void __launch_bounds__(256) sdpa_decode_f16_kernel(const sdpa_geom_t 
 		SDPA_DECODE_SCHED();
 #pragma unroll
 		for (int tt = 0; tt < 2; tt++) {
-			const halfx8 pf = halfx8{ (half_t)s[8 * tt], (half_t)s[8 * tt + 1], (half_t)s[8 * tt + 2], (half_t)s[8 * tt + 3], (half_t)s[8 * tt + 4], (half_t)s[8 * tt + 5], (half_t)s[8 * tt + 6], (half_t)s[8 * tt + 7] };
+			const halfx8 pf = halfx8{ (half_t)s[8 * tt], (half_t)s[8 * tt + 1], (half_t)s[8 * tt + 2], (half_t)s[8 * tt + 3], (half_t)s[8 * tt + 4], (half_t)s[8 * tt + 5], (half_t)s[8 * tt + 6], (half_t)s[8 * tt + 7] }; // (not sdpa_half8: it moves the registers of one instance)
 			const half_t* const blk = Vw + (16 * tt + 4 * lh) * VP + 16 * (li >> 4);
 #pragma unroll
 			for (int t0 = 0; t0 < TV; t0 += TG) { // TG output tiles per wait: the transpose reads are asm, hipcc does not count them
@@ -287,13 +287,8 @@ static int sdpa_decode_f16_run(const sdpa_geom_t& g, const half_t* const qp, con
 	const double kv_bytes = 2.0 * g.B * g.Hk * (double)g.C * (g.D + g.Dv), qo_bytes = 2.0 * g.B * g.Hq * (double)g.R * (g.D + g.Dv);
 	{
 		ProfScope prof("sdpa_fwd_h_decode|nnc::sdpa_decode_f16_kernel", 2.0 * g.B * g.Hq * (double)g.R * g.C * (g.D + g.Dv), kv_bytes + qo_bytes, g.R, g.C, g.D, g.B * g.Hq, (int)splits, stream);
-		const int tv = (g.Dv + 31) / 32;
-#define SDPA_DECODE(DS, TV) hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_decode_f16_kernel<DS, TV>), grid, dim3(256), 0, stream, g, M, qp, kp, vp, mp, op, lse, partial)
-#define SDPA_DECODE_TV(DS) do { if (tv == 1) SDPA_DECODE(DS, 1); else if (tv == 2) SDPA_DECODE(DS, 2); else if (tv <= 4) SDPA_DECODE(DS, 4); else SDPA_DECODE(DS, 8); } while (0)
-		const int ds = (g.D + 15) / 16;
-		if (ds <= 2) SDPA_DECODE_TV(2); else if (ds <= 4) SDPA_DECODE_TV(4); else if (ds <= 8) SDPA_DECODE_TV(8); else if (ds <= 12) SDPA_DECODE_TV(12); else SDPA_DECODE_TV(16);
-#undef SDPA_DECODE_TV
-#undef SDPA_DECODE
+		sdpa_pick(sdpa_ints<2, 4, 8, 12, 16>(), (g.D + 15) / 16, sdpa_ints<1, 2, 4, 8>(), (g.Dv + 31) / 32, [&](auto ds, auto tv) {
+			hipLaunchKernelGGL(HIP_KERNEL_NAME(sdpa_decode_f16_kernel<decltype(ds)::value, decltype(tv)::value>), grid, dim3(256), 0, stream, g, M, qp, kp, vp, mp, op, lse, partial); });
 		HIP_ENFORCE(hipGetLastError());
 	}
 	if (splits > 1) {
