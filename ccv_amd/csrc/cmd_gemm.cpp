@@ -5,6 +5,7 @@
 // instead of the reference's rank-1 GEMM with a ones vector (:158-162), and dbias is a column reduction (:421-431).
 #include "gemm_launch.h"
 #include "gemm_qx_f16.h"
+#include "gemm_rows_f16.h"
 
 using namespace nnc;
 
@@ -237,6 +238,8 @@ static int _gemm_back_f32(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, co
 {
 	return gemm_back_t<float>(cmd, flags, inputs, input_size, outputs, output_size, stream_context, false);
 }
+constexpr int GEMM_ROWS_NOT_TAKEN = 1; // gemm_rows_fused (below, beside gemm_qx_fused): not a command gemm_rows_f16.h takes, nothing was launched
+static int gemm_rows_fused(const ccv_nnc_cmd_t cmd, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context);
 // fp32 -> the fp32 core; half precision throughout and readable in 4-element chunks -> the half-precision core
 // (v_mfma_f32_32x32x16_f16); anything else with a half tensor (mixed types, odd strides) -> the fp32 core on fp32 images
 static int _gemm_forw(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
@@ -244,6 +247,10 @@ static int _gemm_forw(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const 
 	MarkerScope marker(cmd.cmd);
 	const int ut = uniform_float_type(inputs, input_size, outputs, output_size);
 	if (ut == 1) return _gemm_forw_f32(cmd, hint, flags, inputs, input_size, outputs, output_size, stream_context);
+	if (ut == 2) { // a dense layer's few rows: gemm_rows_f16.h where it applies
+		const int taken = gemm_rows_fused(cmd, flags, inputs, input_size, outputs, output_size, stream_context);
+		if (taken != GEMM_ROWS_NOT_TAKEN) return taken;
+	}
 	if (ut == 2 && gemm_forw_t<half_t>(cmd, flags, inputs, input_size, outputs, output_size, stream_context, true) == CCV_NNC_EXEC_SUCCESS)
 		return gemm_forw_t<half_t>(cmd, flags, inputs, input_size, outputs, output_size, stream_context, false);
 	if (!any_half_tensor(inputs, input_size, outputs, output_size)) return CCV_NNC_EXEC_INVALID;
@@ -308,6 +315,30 @@ static int gemm_qx_fused(const ccv_nnc_cmd_t cmd, const int flags, ccv_nnc_tenso
 	if (bias && (!matrix_params(bias, no_transpose, &sm) || sm.outer_nd || sm.batch != 1 || sm.rows != 1 || sm.cols != N || sm.cols_inc != 1)) return GEMM_QX_NOT_TAKEN;
 	MarkerScope marker(cmd.cmd);
 	return gemm_qx_f16_run(w->data.u8, qbits, nib, am.p, am.rows_inc, bias ? sm.p : 0, bm.p, bm.rows_inc, am.rows, N, K, stream_context);
+}
+// A dense layer (ccv_cnnp_dense: lib/nnc/ccv_cnnp_model_addons.c:1368-1373 issues GEMM_FORWARD with transpose_b = (0, 1) against w[N, K]) on at most 32 half rows
+// against a DENSE half weight of at least GEMM_F16_ROWS elements: gemm_rows_f16.h streams the weight from memory into the matrix instruction.  The caller has seen
+// that every tensor is CCV_16F; the operands the kernel reads 16 bytes at a time (a, w: K and the row strides multiples of eight, bases 16-byte aligned; w may be a
+// view with such a row stride) are checked here.  GEMM_ROWS_NOT_TAKEN = any other command: nothing was launched.
+static int gemm_rows_fused(const ccv_nnc_cmd_t cmd, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
+{
+	const long least = tune(TUNE_GEMM_F16_ROWS);
+	if (least <= 0 || (flags & CCV_NNC_ACCUMULATE_OUTPUT) || input_size < 2 || output_size < 1 || !inputs[0] || !inputs[1] || !outputs[0]) return GEMM_ROWS_NOT_TAKEN;
+	const ccv_nnc_tensor_t* const a = inputs[0];
+	const ccv_nnc_tensor_t* const w = inputs[1];
+	const ccv_nnc_tensor_t* const bias = input_size > 2 ? inputs[2] : 0;
+	ccv_nnc_tensor_t* const b = outputs[0];
+	const int* const ta = cmd.info.blas.transpose_a;
+	const int* const tb = cmd.info.blas.transpose_b;
+	if (ta[0] != ta[1] || !((tb[0] == 0 && tb[1] == 1) || (tb[0] == 1 && tb[1] == 0)) || tensor_nd(w->info.dim) != 2) return GEMM_ROWS_NOT_TAKEN;
+	matp_t<half_t> am, wm, bm, sm;
+	if (!matrix_params(a, no_transpose, &am) || !matrix_params(w, no_transpose, &wm) || !matrix_params(b, no_transpose, &bm) || !collapse_rows(&am) || !collapse_rows(&bm)) return GEMM_ROWS_NOT_TAKEN;
+	const int N = wm.rows, K = wm.cols;
+	if (K <= 0 || K % 8 || N <= 0 || N > (1 << 24) || (double)N * (double)K < (double)least) return GEMM_ROWS_NOT_TAKEN;
+	if (am.cols != K || bm.cols != N || am.rows != bm.rows || am.rows < 1 || am.rows > GR_MAX_M) return GEMM_ROWS_NOT_TAKEN;
+	if (am.cols_inc != 1 || am.rows_inc % 8 || ((uintptr_t)am.p & 15) || wm.cols_inc != 1 || wm.rows_inc % 8 || ((uintptr_t)wm.p & 15) || bm.cols_inc != 1) return GEMM_ROWS_NOT_TAKEN;
+	if (bias && (!matrix_params(bias, no_transpose, &sm) || sm.outer_nd || sm.batch != 1 || sm.rows != 1 || sm.cols != N || sm.cols_inc != 1)) return GEMM_ROWS_NOT_TAKEN;
+	return gemm_rows_f16_run(wm.p, wm.rows_inc, am.p, am.rows_inc, bias ? sm.p : 0, bm.p, bm.rows_inc, am.rows, N, K, stream_context);
 }
 // palettized a / w (ccv_nnc_gemm_gpu_cublas.cu:289-334): the fused kernel where it applies, else the dense command on expanded images (palette.cpp)
 static int _gemm_forw_qx(const ccv_nnc_cmd_t cmd, const ccv_nnc_hint_t hint, const int flags, ccv_nnc_tensor_t* const* const inputs, const int input_size, ccv_nnc_tensor_t* const* const outputs, const int output_size, ccv_nnc_stream_context_t* const stream_context)
