@@ -380,6 +380,7 @@ __global__ void __launch_bounds__(256) sdpa_forw_f16_kernel(const sdpa_geom_t g,
 // ---- forward in half precision for every head size in 8s up to 256: sdpa_fwd_anyd_f16_kernel and its launcher ------------------------------------------------
 #include "sdpa_anyd_f16.h"
 #include "sdpa_decode_f16.h"
+#include "sdpa_decode_tiles_f16.h"
 
 // delta[b][h][x] = sum_d g[b, x, h, d] * o[b, x, h, d]   (o: the scratch copy, dense [B][R][Hq][Dv])
 __global__ void __launch_bounds__(256) sdpa_delta_kernel(const sdpa_geom_t g, const float* __restrict__ gr, const long g_sb, const long g_sr, const long g_sh, const float* __restrict__ o, float* __restrict__ delta)
@@ -1084,9 +1085,11 @@ static int sdpa_projection(const sdpa_geom_t& g, ccv_nnc_tensor_t* const c, ccv_
 // SDPA_F16: sdpa_forw_f16_kernel / sdpa_dq_f16_kernel + sdpa_dkv_f16_kernel, which keep the shapes they take; SDPA_ANYD: the kernels of sdpa_anyd_f16.h /
 // sdpa_anyd_f16_back.h for the other head sizes in 8s up to 256 (key SDPA_F16_ANYD: 0 = never, 2 = every shape they can, for measurements); SDPA_DECODE: few query
 // rows against a long cache on sdpa_decode_f16_kernel, in front of both (key SDPA_F16_DECODE: 0 = never, n = from n keys on), forward only and only where the
-// caller allows it: a backward command's forward re-run does not.  chunks: every row read is whole 16-byte chunks, every row written whole 8-byte chunks.
+// caller allows it: a backward command's forward re-run does not; SDPA_DECODE_TILES: under the same conditions, more than one 32-row tile of packed rows per key
+// head on sdpa_decode_tiles_f16_kernel, behind SDPA_DECODE and in front of the other two (key SDPA_DECODE_TILES: the most row tiles, 1 = never).  chunks: every row
+// read is whole 16-byte chunks, every row written whole 8-byte chunks.
 // SDPA_NONE: not on these kernels (the caller goes through fp32 images).
-enum { SDPA_NONE = 0, SDPA_F16, SDPA_ANYD, SDPA_DECODE };
+enum { SDPA_NONE = 0, SDPA_F16, SDPA_ANYD, SDPA_DECODE, SDPA_DECODE_TILES };
 struct sdpa_route_t { int forw, back; };
 static sdpa_route_t sdpa_route_half(const sdpa_geom_t& g, const bool chunks, const bool decode_allowed)
 {
@@ -1095,8 +1098,10 @@ static sdpa_route_t sdpa_route_half(const sdpa_geom_t& g, const bool chunks, con
 	const bool in8s = !(g.D % 8 || g.Dv % 8); // (1 .. 256: sdpa_geometry)
 	const bool forw_f16 = !(g.D % 16 || g.Dv % 32 || g.D > 128 || g.Dv > 128), back_f16 = forw_f16 && g.D % 32 == 0;
 	const auto family = [&](const bool f16) { return anyd && in8s && (anyd == 2 || !f16) ? SDPA_ANYD : f16 ? SDPA_F16 : SDPA_NONE; };
-	const bool use_decode = decode_allowed && decode > 0 && in8s && (long)g.R * g.ratio <= SDPA_DECODE_ROWS && g.C >= decode;
-	return { use_decode ? SDPA_DECODE : family(forw_f16), family(back_f16) };
+	const long rows = (long)g.R * g.ratio, tiles = tune(TUNE_SDPA_DECODE_TILES) < SDPA_DECODE_TILES_MAX ? tune(TUNE_SDPA_DECODE_TILES) : SDPA_DECODE_TILES_MAX;
+	const bool decode_shape = decode_allowed && decode > 0 && in8s && g.C >= decode;
+	const bool use_decode = decode_shape && rows <= SDPA_DECODE_ROWS, use_tiles = decode_shape && rows > SDPA_DECODE_ROWS && rows <= SDPA_DECODE_ROWS * tiles;
+	return { use_decode ? SDPA_DECODE : use_tiles ? SDPA_DECODE_TILES : family(forw_f16), family(back_f16) };
 }
 static void sdpa_forw_f16_launch(const sdpa_geom_t& g, const half_t* const qp, const half_t* const kp, const half_t* const vp, const half_t* const mp, half_t* const op, float* const lse, hipStream_t stream)
 {
@@ -1143,8 +1148,8 @@ static int sdpa_forw_half(EXEC_ARGS)
 	MarkerScope marker(cmd.cmd);
 	if (!g.R || !g.Hq || !g.B) return CCV_NNC_EXEC_SUCCESS;
 	const half_t* const mp = mask ? (const half_t*)mask->data.u8 : 0;
-	if (family == SDPA_DECODE) {
-		const int r = sdpa_decode_f16_run(g, (const half_t*)qi.p, (const half_t*)ki.p, (const half_t*)vi.p, mp, (half_t*)ci.p, lse, stream_context);
+	if (family == SDPA_DECODE || family == SDPA_DECODE_TILES) {
+		const int r = (family == SDPA_DECODE ? sdpa_decode_f16_run : sdpa_decode_tiles_f16_run)(g, (const half_t*)qi.p, (const half_t*)ki.p, (const half_t*)vi.p, mp, (half_t*)ci.p, lse, stream_context);
 		if (r != CCV_NNC_EXEC_SUCCESS) return r;
 	} else (family == SDPA_ANYD ? sdpa_fwd_anyd_f16_launch : sdpa_forw_f16_launch)(g, (const half_t*)qi.p, (const half_t*)ki.p, (const half_t*)vi.p, mp, (half_t*)ci.p, lse, stream_of(stream_context));
 	if (!w) return CCV_NNC_EXEC_SUCCESS;

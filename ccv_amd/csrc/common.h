@@ -290,6 +290,7 @@ enum {
 	TUNE_SDPA_DECODE_SPLITS, // ... its splits of the key axis: 0 = chosen by the launch, n = n splits (tests, measurements)
 	TUNE_GEMM_F16_ROWS,     // GEMM_FORWARD of at most 32 CCV_16F rows against a dense CCV_16F weight [N, K] (transpose_b: the dense layer's form) streams the weight from memory straight into the matrix instruction (gemm_rows_f16.h): n > 0 = when the weight has at least n elements (N K >= n; 1 = every size), 0 = never (the 64 x 64 tile of the contraction core, split-K and its fold).  Default 0: faster than that route on two of seventeen measured rows only
 	TUNE_GEMM_F16_ROWS_SLICES, // ... its slices of K: 0 = chosen by the launch, n = n slices (tests, measurements)
+	TUNE_SDPA_DECODE_TILES, // SCALED_DOT_PRODUCT_ATTENTION_FORWARD on CCV_16F tensors with MORE than 32 packed rows per key head on the row-tile split-key kernel of sdpa_decode_tiles_f16.h: n = the most 32-row tiles per key head that take it (32 < R ratio <= 32 n, n at most 8), under the other conditions of SDPA_F16_DECODE (that key above 0, at least that many keys); the splits follow SDPA_DECODE_SPLITS.  Default 1: never (the other half forward kernels)
 	TUNE_COUNT
 };
 static_assert(TUNE_GRID_WG_PER_CU == 3, "grid_for() above names this key by value");

@@ -4,7 +4,10 @@ against a key / value cache of C keys -- each as ONE command through the command
 the median of `--repeats` windows of at least `--window-ms`, their spread (max - min), and the compulsory bytes (K and V once per key head, q and o) per second.
 Uses nothing but the command interface and tune_set, so it runs on a build without sdpa_decode_f16_kernel (--lib, where the keys do not exist and are left alone):
 both sides of a comparison come from this script, run alternately, and --report lays the runs side by side.
-usage: python tools/attention_decode_bench.py [--lib PATH] [--label NAME] [--decode 1] [--splits 0] [--repeats 11] [--window-ms 200] [--json OUT]
+--tiles N sets SDPA_DECODE_TILES (sdpa_decode_tiles_f16_kernel for up to 32 N packed rows per key head) and times the rows with 40 .. 256 packed rows in place of
+the decode rows: the comparison is then the SAME library with --tiles 1 --label parent (the former routes) against --tiles 8.  --min-blocks N forces on each of those
+rows the split count the launch's rule gives with N blocks as the shortest split (the rule restated here), to measure the rule's constant.
+usage: python tools/attention_decode_bench.py [--lib PATH] [--label NAME] [--decode 1] [--splits 0] [--tiles N [--min-blocks N]] [--repeats 11] [--window-ms 200] [--json OUT]
        python tools/attention_decode_bench.py --report NEW1.json PARENT1.json [NEW2.json PARENT2.json]"""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,15 +18,27 @@ COPY_RATE = 6.29e12  # bytes per second of a device copy, DESIGN.md section 5
 # B, R, C, Hq, Hk, D
 SHAPES = [(b, 1, c, 32, 8, 128) for b in (1, 8) for c in (128, 256, 512, 2048, 8192, 32768)]
 SHAPES += [(1, 1, 2048, 16, 16, 64), (1, 1, 8192, 8, 1, 256), (1, 4, 8192, 32, 8, 128), (1, 128, 8192, 32, 8, 128)]  # multi-head, multi-query, speculative, the control
+# --tiles: 40, 64, 128 and 256 packed rows per key head (verification of a speculated run, a chunked prefill's tail), multi-query with two rows, a batch of eight
+TILE_SHAPES = [(1, r, c, 32, 8, 128) for r in (10, 16, 32, 64) for c in (512, 2048, 8192, 32768)] + [(1, 2, 8192, 32, 1, 128), (8, 8, 2048, 32, 8, 128)]
+
+
+def rule_splits(shape, min_blocks, cus=256):
+    """The split count sdpa_decode_tiles_f16_run chooses, with `min_blocks` in place of its shortest split."""
+    B, R, C, Hq, Hk, D = shape
+    M = R * (Hq // Hk)
+    wgs = B * Hk * -(-M // (64 if M <= 64 else 128))
+    return max(1, min(1 if wgs >= cus else -(-cus // wgs), ((C + 31) // 32) // min_blocks))
 
 
 def measure(args):
     from ccv_amd import nnc
     L = nnc.load(args.lib)
     print("library", L.dll.nnc_mi355x_version().decode(), args.lib or "")
-    if args.label != "parent":
+    if args.label != "parent" or args.tiles:
         L.tune_set("SDPA_F16_DECODE", args.decode)
         L.tune_set("SDPA_DECODE_SPLITS", args.splits)
+    if args.tiles:
+        L.tune_set("SDPA_DECODE_TILES", args.tiles)
     s = L.stream_new(0)
     e0, e1 = L.dll.nnc_mi355x_event_new(), L.dll.nnc_mi355x_event_new()
     L.dll.nnc_mi355x_event_elapsed_ms.restype = nnc.C.c_float
@@ -42,8 +57,10 @@ def measure(args):
 
     out = []
     print("(B,R,C,Hq,Hk,D) median ms (spread) | compulsory TB/s | launches")
-    for shape in SHAPES:
+    for shape in (TILE_SHAPES if args.tiles else SHAPES):
         B, R, C, Hq, Hk, D = shape
+        if args.tiles and args.min_blocks:
+            L.tune_set("SDPA_DECODE_SPLITS", rule_splits(shape, args.min_blocks))
         cmd = nnc.generic_cmd("SCALED_DOT_PRODUCT_ATTENTION_FORWARD")
         cmd.info.f1.v = float(1.0 / np.sqrt(D))  # scaled_dot_product_attention.scale
         ins, outs = [dev(B, R, Hq, D), dev(B, C, Hk, D), dev(B, C, Hk, D)], [dev(B, R, Hq, D)]
@@ -62,7 +79,7 @@ def measure(args):
         print("%-28s %9.4f ms (%.4f) | %6.3f | %s" % (out[-1]["row"], med, spread, nbytes / med / 1e9, ",".join(launches)), flush=True)
     if args.json:
         with open(args.json, "w") as f:
-            json.dump(dict(label=args.label, decode=args.decode, splits=args.splits, rows=out), f)
+            json.dump(dict(label=args.label, decode=args.decode, splits=args.splits, tiles=args.tiles, min_blocks=args.min_blocks, rows=out), f)
 
 
 def report(paths):
@@ -90,6 +107,8 @@ def main():
     ap.add_argument("--label", default="this tree", help="'parent' for the parent commit's build (the tuning keys are then left alone)")
     ap.add_argument("--decode", type=int, default=1, help="the SDPA_F16_DECODE tuning key")
     ap.add_argument("--splits", type=int, default=0, help="the SDPA_DECODE_SPLITS tuning key")
+    ap.add_argument("--tiles", type=int, default=0, help="the SDPA_DECODE_TILES tuning key; the rows are then those with 40 .. 256 packed rows per key head")
+    ap.add_argument("--min-blocks", type=int, default=0, help="with --tiles: force the splits of the launch's rule with this shortest split, in 32-key blocks")
     ap.add_argument("--repeats", type=int, default=11, help="timed windows per row: the median and the spread are reported")
     ap.add_argument("--window-ms", type=float, default=200.0, help="least work timed per window")
     ap.add_argument("--json", default=None, help="also write the rows to this file")
